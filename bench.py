@@ -16,6 +16,9 @@ Legs, in this order (rank 0 prints ONE compact JSON line at the very end, nothin
   1. warm-up (W tiles), then the TIMED region: exactly K tile-steps, no per-launch instrumentation.  The accumulation
      phase is aligned so that the K-th tile ends an optimizer step: the region holds ceil(K / (optimize_every/world))
      all-reduce + AdamW steps -- never fewer per tile than the reference's one per 64 tiles.
+     ``--dump-outputs DIR``: what the timed region's last step left to its caller, as DIR/<name>.npy (see dump_outputs).
+  A plain run (``--gpus N --steps K --warmup W``) stops here: it prints the line with `value` and `ms_per_step` of the timed
+  region.  Everything below is measured only with ``--full`` (or where its own option is given a value explicitly):
   1b. sustained leg (untimed for `value`): ``--sustain-s`` seconds of back-to-back tile-steps, one HIP event per step
      -> ``sustained`` (ms/step over seconds, first vs last quartile of the per-step GPU times).
   2. profile leg (untimed): ``--profile-steps`` more tile-steps with two HIP events around every C-ABI launch, on the
@@ -25,7 +28,8 @@ Legs, in this order (rank 0 prints ONE compact JSON line at the very end, nothin
      The trainer's overlaps (weight gradients on a side stream beside the data-gradient chain; tile i + 1's forward beside tile
      i's backward -- both on in the timed region) are OFF in this leg: a kernel's two events then bracket that kernel alone
      (profiles/run_profiles.sh runs the profiler passes the same way).
-  3. ``--check-dp`` (optional): the data-parallel equivalence check of SURVEY.md 8e.
+  2b. the cost of one optimizer boundary on its own (`optimizer_boundary_ms`).
+  3. ``--check-dp``: the data-parallel equivalence check of SURVEY.md 8e (by default with ``--full`` when N > 1).
   4. cpu_baseline (rank 0, N = 1 only): the oracle torch restatement on the host cores, SURVEY.md 8d protocol.
 """
 import argparse
@@ -70,14 +74,15 @@ def parse():
     ap.add_argument("--tile-pool", type=int, default=4, help="distinct resident tiles cycled per rank")
     ap.add_argument("--channels-last", type=int, default=1, help="grid side in NHWC (same numerics, no layout copies)")
     ap.add_argument("--miopen-find", type=int, default=0, help="torch.backends.cudnn.benchmark")
-    ap.add_argument("--profile-steps", type=int, default=16,
-                    help="untimed tile-steps with per-launch HIP events after the timed region (0 = no kernel table)")
+    ap.add_argument("--profile-steps", type=int, default=None,
+                    help="untimed tile-steps with per-launch HIP events after the timed region (0 = no kernel table; "
+                         "default 16 with --full, else 0)")
     ap.add_argument("--kernel-table", default=os.path.join("gpurun_out", "bench_kernels.json"),
                     help="where rank 0 writes the full per-kernel table (never printed: the stdout line stays compact)")
     ap.add_argument("--tile-prefetch", type=int, default=0,
                     help="build the next tile's point index on a side stream during the current step (Trainer.prepare); "
                          "measured slower (12.20 vs 11.97 ms: like every two-stream overlap tried on this stack), so off")
-    ap.add_argument("--skip-cpu-baseline", action="store_true")
+    ap.add_argument("--skip-cpu-baseline", action="store_true", help="no CPU baseline leg (it runs only with --full)")
     ap.add_argument("--cpu-threads", type=int, default=8, help="intra-op threads of the headline CPU baseline "
                                                                 "(reference default: conf/config.yaml:20-21, train.py:77-78)")
     ap.add_argument("--cpu-max-threads", type=int, default=64, help="thread cap of the all-cores CPU leg")
@@ -101,9 +106,10 @@ def parse():
     ap.add_argument("--coalesce", type=int, default=-1,
                     help="tiles Trainer.train_step(tile) holds back and issues as one ragged micro-batch (Trainer.coalesce_tiles; "
                          "-1 = the Trainer's default, T2H_COALESCE_TILES or 4; 1 = the strict B = 1 step, also reported as `strict_b1`)")
-    ap.add_argument("--strict-b1-steps", type=int, default=16,
+    ap.add_argument("--strict-b1-steps", type=int, default=None,
                     help="tile-steps of a short timed leg with coalescing off (every train_step call issues its own tile: the B = 1 "
-                         "step of rounds 1-5); reported as `strict_b1`, never part of `value` (0: skip)")
+                         "step of rounds 1-5); reported as `strict_b1`, never part of `value` (0: skip; default 16 with --full, "
+                         "else 0)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl = RCCL over xGMI (the real multi-GPU run); gloo only to smoke-test the N>1 code path "
                          "with several ranks sharing one GPU")
@@ -114,22 +120,26 @@ def parse():
     ap.add_argument("--check-dp", type=int, default=-1,
                     help="SURVEY 8e equivalence check: the W-rank accumulated + all-reduced gradient of 2W fixed tiles vs "
                          "the same tiles accumulated by one rank alone; reports max_rel_diff, allreduce_ms, rccl_ranks.  "
-                         "-1 (default): on whenever N > 1 (it runs after the timed region and costs < 1 s), 0 / 1: off / on")
+                         "-1 (default): on with --full whenever N > 1 (it runs after the timed region and costs < 1 s), "
+                         "0 / 1: off / on")
     ap.add_argument("--fused-optimizer", type=int, default=1, help="1 = t2h flat-bucket AdamW kernel, 0 = torch.optim.AdamW")
-    ap.add_argument("--sustain-s", type=float, default=6.0,
+    ap.add_argument("--sustain-s", type=float, default=None,
                     help="after the timed region: this many seconds of back-to-back tile-steps (one HIP event per step, nothing "
-                         "else) -> sustained_ms_per_step and first / last quartile step time; never part of `value`.  0 = off")
+                         "else) -> sustained_ms_per_step and first / last quartile step time; never part of `value`.  0 = off "
+                         "(default 6 with --full, else 0)")
     ap.add_argument("--pin-cores", type=int, default=1,
                     help="N > 1: bind every rank to its own CPU cores (NUMA-local to its GPU where sysfs tells) before the GPU is "
                          "initialised; 0 = leave the affinity alone")
-    ap.add_argument("--micro-batch-steps", type=int, default=32,
+    ap.add_argument("--micro-batch-steps", type=int, default=None,
                     help="tile-steps of a THIRD short timed leg with the accumulation window micro-batched: 4 tiles of different "
                          "point counts per forward / backward (Trainer.train_step([tiles]): the same accumulated gradient to fp32 "
-                         "re-association); reported as `micro_batched`, never part of `value` (0: skip; only with --train-batch 1)")
-    ap.add_argument("--exact-split-steps", type=int, default=16,
+                         "re-association); reported as `micro_batched`, never part of `value` (0: skip; only with --train-batch 1; "
+                         "default 32 with --full, else 0)")
+    ap.add_argument("--exact-split-steps", type=int, default=None,
                     help="tile-steps of a SECOND short timed leg with the 3x3 / transposed convolutions on the exact three-way bf16 "
                          "split (six MFMAs per product: fp32 arithmetic bit for bit up to summation order) instead of the default "
-                         "two-way fp16 split with block scales; reported as `exact_split`, never part of `value` (0: skip)")
+                         "two-way fp16 split with block scales; reported as `exact_split`, never part of `value` (0: skip; "
+                         "default 16 with --full, else 0)")
     ap.add_argument("--from-producer", action="store_true",
                     help="every tile of every leg is cropped / normalised / augmented / raster-patched on the device by "
                          "producer.TileSource from a synthetic chunk resident in HBM (dataset.py:201-330) inside the loop, "
@@ -138,7 +148,22 @@ def parse():
     ap.add_argument("--producer-prefetch", type=int, default=1,
                     help="--from-producer: 1 = tile i + 1 is produced on a side stream while step i runs (the overlap the "
                          "reference gets from DataLoader workers), 0 = produce, then train, in sequence on one stream")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beyond the headline: sustained, exact_split, strict_b1 and micro_batched legs, the "
+                         "per-kernel profile leg and rooflines, the optimizer-boundary timing, --check-dp for N > 1 and the CPU "
+                         "baseline.  Off: the run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what its last step computed as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all; larger outputs as a fixed seeded sample)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    # the extra legs: their own defaults with --full, off otherwise (a value given on the command line always holds)
+    for name, full_default in (("profile_steps", 16), ("sustain_s", 6.0), ("strict_b1_steps", 16), ("micro_batch_steps", 32),
+                               ("exact_split_steps", 16)):
+        if getattr(args, name) is None:
+            setattr(args, name, full_default if args.full else 0)
+    return args
 
 
 def pmc_traffic():
@@ -206,6 +231,54 @@ def point_update_note():
     if deferred.DEFER_MIN_CHANNELS > 0:
         parts.append(f"fc_comm.2 / fc_c on per-cell sums from >= {deferred.DEFER_MIN_CHANNELS} channels on")
     return "; ".join(parts) if parts else "point-wise as the reference (alto.py:121-130)"
+
+
+DUMP_BUDGET_BYTES = 60_000_000     # --dump-outputs: all files together stay below 64 MB
+DUMP_SAMPLE_SEED = 20240601
+
+
+def dump_outputs(path, arrays):
+    """Write ``arrays`` ({name: tensor or array}) as path/<name>.npy, floating point as float32 (float64 stays float64).  If they
+    exceed DUMP_BUDGET_BYTES together, every array of more than 2**20 elements is replaced by the same fraction of its elements,
+    drawn by a fixed seed from its flat index range (depends only on its length: the same elements in every run and build).
+    Returns {name: [elements written, elements computed]}."""
+    import numpy as np
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        host[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in host.values())
+    frac = min(1.0, DUMP_BUDGET_BYTES / max(total, 1))
+    os.makedirs(path, exist_ok=True)
+    written = {}
+    for name, a in host.items():
+        n = a.size
+        if frac < 1.0 and n > 2 ** 20:
+            keep = np.random.default_rng(DUMP_SAMPLE_SEED).random(n) < frac * 0.99
+            a = a.reshape(-1)[keep]
+        np.save(os.path.join(path, name + ".npy"), a)
+        written[name] = [int(a.size), int(n)]
+    return written
+
+
+def train_outputs(model, trainer, reduced_grad):
+    """What a caller of ``Trainer.train_step`` holds after the timed region's last step (which ends an optimizer step): the
+    updated parameters, the averaged losses of that window, and the accumulated (all-reduced) gradient the optimizer consumed.
+    Parameters and gradients are flattened in ``model.parameters()`` order, each tensor in its logical (contiguous) element
+    order, so that the files do not depend on memory layouts or on the gradient bucket's padding."""
+    out = {"params": torch.cat([p.detach().contiguous().reshape(-1) for p in model.parameters()]),
+           "loss": torch.as_tensor(trainer.last_avg_loss, dtype=torch.float64).reshape(1)}
+    for k, v in trainer.last_avg_loss_dict.items():
+        out[k] = torch.as_tensor(v, dtype=torch.float64).reshape(1)
+    if reduced_grad is not None:
+        flat = trainer.bucket.flat
+        grads = []
+        for p in trainer.bucket.params:            # (the parameters that receive a gradient, in model order)
+            g = p.grad
+            view = torch.as_strided(reduced_grad, g.size(), g.stride(), g.storage_offset() - flat.storage_offset())
+            grads.append(view.contiguous().reshape(-1))
+        out["grad"] = torch.cat(grads)
+    return out
 
 
 def cpu_baseline(args):
@@ -287,6 +360,8 @@ def infer_bench(args, world, rank, dev, group):
         with torch.no_grad(), torch.cuda.graph(graph):
             static_out = model(input_cloud=static_cloud, input_image=static_image)  # noqa: F841 (kept alive by the graph)
 
+    last = {}
+
     def run(n, off=0):
         with torch.no_grad():
             for s in range(n):
@@ -295,8 +370,11 @@ def infer_bench(args, world, rank, dev, group):
                     static_cloud.copy_(cloud, non_blocking=True)
                     static_image.copy_(image, non_blocking=True)
                     graph.replay()
+                    out = static_out
                 else:
-                    model(input_cloud=cloud, input_image=image)
+                    out = model(input_cloud=cloud, input_image=image)
+                if args.dump_outputs:
+                    last["out"] = out                  # (kept only when asked for: the plain loop frees every output at once)
 
     def fence():
         torch.cuda.synchronize()
@@ -314,6 +392,10 @@ def infer_bench(args, world, rank, dev, group):
         tmax = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if rank == 0 and args.dump_outputs:
+        # the last timed forward's result, as its caller receives it: heights and footprint logits of the batch's tiles
+        pa, pb = last["out"]
+        dump_outputs(args.dump_outputs, {"heights": pa} if pb is None else {"heights": pa, "footprint_logits": pb})
     if rank == 0:
         print(json.dumps({
             "metric": "inference tiles/sec (Munich cloud+image+footprint, forward only)",
@@ -672,6 +754,12 @@ def main():
     # work of ceil(K / local_every) optimizer steps (the driver's K = 20 would otherwise never reach the 64th tile)
     le = trainer.local_every
     trainer.accumulated_steps = (le - args.steps % le) % le
+    reduced = {}
+    if args.dump_outputs:
+        # the gradient the last optimizer step consumes is zeroed by that step: one device copy per boundary keeps it
+        def keep_reduced(flat):
+            reduced["grad"] = flat.clone()
+        trainer.on_reduced = keep_reduced
     fence()
     steps_before, points_before = state["optimizer_steps"], state["points"]
     t0 = time.perf_counter()
@@ -684,6 +772,11 @@ def main():
         tmax = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if args.dump_outputs:
+        trainer.on_reduced = None
+        if rank == 0:                                   # (the replicas hold the same parameters, losses and reduced gradient)
+            dump_outputs(args.dump_outputs, train_outputs(model, trainer, reduced.get("grad")))
+        reduced.clear()
 
     # ---- leg 1b: sustained run (never part of `value`): does the rate of the short timed region hold over seconds?
     sustained = None
@@ -847,16 +940,18 @@ def main():
         finally:
             trainer.overlap_wgrad, trainer.overlap_conv_wgrad, trainer.pipeline_tiles = saved_overlap
     # one optimizer boundary on its own (all-reduce + AdamW + bucket zero), between two events on the compute stream
-    fence()
-    eb, ee = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    eb.record()
-    trainer.optimizer_boundary()
-    ee.record()
-    fence()
-    boundary_ms = eb.elapsed_time(ee)
+    boundary_ms = None
+    if args.full:
+        fence()
+        eb, ee = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        eb.record()
+        trainer.optimizer_boundary()
+        ee.record()
+        fence()
+        boundary_ms = eb.elapsed_time(ee)
 
     dp = None
-    if args.check_dp == 1 or (args.check_dp < 0 and world > 1):
+    if args.check_dp == 1 or (args.check_dp < 0 and world > 1 and args.full):
         try:
             dp = check_dp(args, world, rank, dev, group, model, make_trainer)
             if args.backend == "nccl" and world > 1 and dp.get("rccl_ranks") != world:
@@ -864,7 +959,7 @@ def main():
         except Exception as e:          # the headline line must survive a failing diagnostic (every rank fails alike or the
             dp = {"error": f"{type(e).__name__}: {e}"[:300]}      # collective inside raises on all of them)
     per_rank = None
-    if world > 1:
+    if world > 1 and args.full:
         # what every rank's HOST did (the scaling risk of the line: DESIGN section 6): its cores and its CPU time per tile-step
         mine = {"rank": rank, "cpus": os.environ.get("T2H_RANK_CPUS", ""),
                 "host_cpu_ms_per_step": None if sustained is None else sustained["host_cpu_ms_per_step"],
@@ -895,7 +990,6 @@ def main():
                        "points_per_tile": args.points, "optimize_every": args.optimize_every, "train_batch": args.train_batch,
                        "coalesce_tiles": co,
                        "optimizer_steps_in_timed_region": timed_optimizer_steps, "optimizer": opt_name,
-                       "optimizer_boundary_ms": round(boundary_ms, 3),
                        "parallelism": f"dp{world}", "collective": (dist.get_backend(group) if world > 1 else None),
                        "rccl_ranks": world if (world > 1 and dist.get_backend(group) == "nccl") else 0,
                        "channels_last": bool(args.channels_last),
@@ -911,6 +1005,8 @@ def main():
                        "library_fallbacks": getattr(grid, "fallback_count", lambda: None)(),
                        "hip_graph": bool(args.hip_graph)},
         }
+        if boundary_ms is not None:
+            out["config"]["optimizer_boundary_ms"] = round(boundary_ms, 3)
         if args.mlp_precision != "fp32":
             from tomosar2height_amd import mlp
             out["config"]["trunk_precision"] = mlp.trunk_precision()
@@ -987,7 +1083,7 @@ def main():
                             "affinity_disjoint": bool(all(sets)) and all(not (sets[i] & sets[j]) for i in range(world)
                                                                          for j in range(i + 1, world)),
                             "first_cpu": [min((int(c) for c in st), default=-1) for st in sets]}
-        if world == 1 and not args.skip_cpu_baseline:
+        if world == 1 and args.full and not args.skip_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args)          # last: the GPU legs above run back to back
         print(json.dumps(out), flush=True)
     if world > 1:

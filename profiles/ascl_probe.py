@@ -9,7 +9,7 @@ def spy(x):
         seen[(tuple(x.shape), tuple(x.stride()), " <- ".join(f"{f.name}:{f.lineno}" for f in fr))] += 1
     return orig(x)
 grid._as_cl = spy
-sys.argv = ["bench.py", "--steps", "10", "--warmup", "2", "--skip-cpu-baseline", "--profile-steps", "0", "--sustain-s", "0"]
+sys.argv = ["bench.py", "--full", "--steps", "10", "--warmup", "2", "--skip-cpu-baseline", "--profile-steps", "0", "--sustain-s", "0"]
 import bench
 bench.main()
 for k, v in seen.most_common(20): print(v, k, file=sys.stderr)

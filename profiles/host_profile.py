@@ -12,7 +12,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 torch.autograd.set_multithreading_enabled(False)
 STEPS = 60
-sys.argv = ["bench.py", "--steps", str(STEPS), "--warmup", "5", "--skip-cpu-baseline", "--profile-steps", "0", "--sustain-s", "0"] + sys.argv[1:]
+sys.argv = ["bench.py", "--full", "--steps", str(STEPS), "--warmup", "5", "--skip-cpu-baseline", "--profile-steps", "0", "--sustain-s", "0"] + sys.argv[1:]
 import bench  # noqa: E402
 
 pr = cProfile.Profile()

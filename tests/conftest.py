@@ -1,3 +1,4 @@
+import glob
 import os
 import sys
 
@@ -30,8 +31,38 @@ def pytest_sessionstart(session):
         print(f"[conftest] library pre-build skipped: {e}")
 
 
+class _GoldenParts:
+    """The arrays of a fixture stored as name.part1.npz, name.part2.npz, ... (every committed file stays below 1 MiB; see
+    tests/golden/make_golden.py:split_large), read like one ``np.load`` result: ``g[key]``, ``g.files``, ``key in g``."""
+
+    def __init__(self, paths):
+        self._arrays = {}
+        for p in paths:
+            with np.load(p, allow_pickle=False) as part:
+                self._arrays.update({k: part[k] for k in part.files})
+        self.files = list(self._arrays)
+
+    def __getitem__(self, key):
+        return self._arrays[key]
+
+    def __contains__(self, key):
+        return key in self._arrays
+
+    def __iter__(self):
+        return iter(self.files)
+
+    def keys(self):
+        return self.files
+
+
 def load_golden(name):
-    return np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
+    path = os.path.join(GOLDEN, name + ".npz")
+    if os.path.exists(path):
+        return np.load(path, allow_pickle=False)
+    parts = sorted(glob.glob(os.path.join(GOLDEN, name + ".part*.npz")), key=lambda p: int(p.rsplit(".part", 1)[1][:-4]))
+    if not parts:
+        raise FileNotFoundError(path)
+    return _GoldenParts(parts)
 
 
 @pytest.fixture(autouse=True)

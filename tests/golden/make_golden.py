@@ -35,6 +35,40 @@ def save(name, **arrays):
     path = os.path.join(HERE, name + ".npz")
     np.savez_compressed(path, **out)
     print(f"wrote {name}.npz  ({os.path.getsize(path) / 1024:.1f} KiB)")
+    split_large(name)
+
+
+PART_BYTES = 1_000_000       # every committed file stays below 1 MiB
+
+
+def split_large(name):
+    """A fixture larger than PART_BYTES is rewritten as name.part1.npz, name.part2.npz, ... (the same arrays, greedily packed by
+    their compressed size; tests/conftest.py:load_golden merges them)."""
+    import glob
+    import zipfile
+    path = os.path.join(HERE, name + ".npz")
+    if os.path.getsize(path) <= PART_BYTES:
+        return
+    for old in glob.glob(os.path.join(HERE, name + ".part*.npz")):
+        os.remove(old)
+    with zipfile.ZipFile(path) as z:
+        sizes = {i.filename[:-4]: i.compress_size + 2 * len(i.filename) + 200 for i in z.infolist()}    # (+ zip headers)
+    with np.load(path, allow_pickle=False) as g:
+        arrays = {k: g[k] for k in g.files}
+    parts, cur, used = [], {}, 0
+    for k in arrays:                                   # (stored order kept)
+        if cur and used + sizes[k] > PART_BYTES - 4096:
+            parts.append(cur)
+            cur, used = {}, 0
+        cur[k] = arrays[k]
+        used += sizes[k]
+    parts.append(cur)
+    for i, part in enumerate(parts, 1):
+        p = os.path.join(HERE, f"{name}.part{i}.npz")
+        np.savez_compressed(p, **part)
+        assert os.path.getsize(p) < 2 ** 20, p
+    os.remove(path)
+    print(f"  split into {len(parts)} parts")
 
 
 def edge_xy(m, seed):

@@ -50,6 +50,35 @@ def test_printed_line_stays_compact():
     assert len(json.dumps(out)) < 4096
 
 
+def test_legs_beyond_the_headline_run_only_with_full(monkeypatch):
+    legs = ("profile_steps", "sustain_s", "strict_b1_steps", "micro_batch_steps", "exact_split_steps")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "3"])
+    plain = bench.parse()
+    assert plain.steps == 7 and plain.warmup == 3 and not plain.full and plain.dump_outputs is None
+    assert all(getattr(plain, k) == 0 for k in legs)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    full = bench.parse()
+    assert full.full and full.dump_outputs == "out"
+    assert [getattr(full, k) for k in legs] == [16, 6.0, 16, 32, 16]
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--profile-steps", "2", "--sustain-s", "0", "--full"])
+    given = bench.parse()                       # a value on the command line holds, with or without --full
+    assert given.profile_steps == 2 and given.sustain_s == 0 and given.exact_split_steps == 16
+
+
+def test_dump_budget_and_fixed_sample(tmp_path):
+    import numpy as np
+    import torch
+    big = {"params": torch.arange(12_000_000, dtype=torch.float32), "grad": torch.ones(11_000_000),
+           "loss": torch.tensor([2.5], dtype=torch.float64)}
+    written = bench.dump_outputs(str(tmp_path / "a"), big)
+    bench.dump_outputs(str(tmp_path / "b"), big)
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert total <= 64_000_000 and written["loss"] == [1, 1] and written["params"][0] < 12_000_000
+    a, b = np.load(tmp_path / "a" / "params.npy"), np.load(tmp_path / "b" / "params.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, b) and np.all(np.diff(a) > 0)       # the same elements, in order
+    assert np.load(tmp_path / "a" / "loss.npy").dtype == np.float64
+
+
 def test_gpus_n_without_a_launcher_starts_its_own_ranks():
     """`python bench.py --gpus 2` the way the driver calls it: the ranks must be started as a child torch.distributed.run
     (here, without a GPU, each rank then refuses to run -- which proves they were started, with the command line

@@ -85,7 +85,7 @@ def test_multi_rank_mosaic_equals_single(tmp_path):
 @pytest.mark.gpu
 def test_bench_two_ranks_check_dp_line_is_compact():
     r = _launch(2, [os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu", "--steps", "4",
-                    "--warmup", "1", "--points", "8192", "--optimize-every", "4", "--profile-steps", "2",
+                    "--warmup", "1", "--points", "8192", "--optimize-every", "4", "--profile-steps", "2", "--full",
                     "--kernel-table", os.path.join(ROOT, "gpurun_out", "bench_kernels_test.json")])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1 and r.stdout.rstrip().endswith(lines[0]), "the JSON line must be the last thing on stdout"
@@ -104,7 +104,7 @@ def test_bench_gpus_two_without_a_launcher():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(HSA_ENABLE_IPC_MODE_LEGACY="0", OMP_NUM_THREADS="4")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu", "--steps", "4",
-           "--warmup", "1", "--points", "8192", "--optimize-every", "4", "--profile-steps", "2", "--sustain-s", "0",
+           "--warmup", "1", "--points", "8192", "--optimize-every", "4", "--profile-steps", "2", "--sustain-s", "0", "--full",
            "--kernel-table", os.path.join(ROOT, "gpurun_out", "bench_kernels_test.json")]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, f"--- stdout\n{r.stdout[-4000:]}\n--- stderr\n{r.stderr[-6000:]}"
@@ -127,7 +127,7 @@ def test_bench_eight_ranks_dry_run_on_one_gpu():
     env.pop("OMP_NUM_THREADS", None)                      # bench.py's launcher sets cores / ranks
     out = os.path.join(ROOT, "gpurun_out", "bench_8rank_dry_run.json")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--backend", "gloo", "--share-gpu", "--steps", "8",
-           "--warmup", "2", "--profile-steps", "0", "--sustain-s", "2"]
+           "--warmup", "2", "--profile-steps", "0", "--sustain-s", "2", "--full"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, f"--- stdout\n{r.stdout[-4000:]}\n--- stderr\n{r.stderr[-6000:]}"
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
