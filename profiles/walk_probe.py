@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A/B probe of the on-chip hidden-activation kernels (t2h_sample_relu_cellsums2 / t2h_sample_bwd_from_sums) at the three
-shapes of the benchmarked step (N = 131072 clustered points): the r04 kernels against the r05 ones (environment switches read
-per call), outputs compared bit for bit, durations by HIP events (median of REPS launches, kernels alone).
+shapes of the benchmarked step (N = 131072 clustered points): without and with the dispatch order (t2h_cell_order_build),
+outputs compared bit for bit, durations by HIP events (median of REPS launches, kernels alone).
 
     python3 profiles/walk_probe.py            # prints one line per (kernel, shape, variant)
 """
@@ -17,7 +17,7 @@ from tomosar2height_amd.synthetic import berlin_tile          # noqa: E402
 from tomosar2height_amd.tile import TileIndex                 # noqa: E402
 
 REPS = int(os.environ.get("REPS", "30"))
-FWD = [v for v in os.environ.get("FWD_VARIANTS", "0,1,1o").split(",") if v]     # 0 = r04 kernel, 1 = r05, o = + dispatch order
+FWD = [v for v in os.environ.get("FWD_VARIANTS", "1,1o").split(",") if v]       # o = + dispatch order
 BWD = [v for v in os.environ.get("BWD_VARIANTS", "1,1o").split(",") if v]      # (r05 kernel without / with the dispatch order)
 dev = torch.device("cuda:0")
 tile = TileIndex(berlin_tile(1000, clustered=os.environ.get("UNIFORM", "0") != "1")["inputs"].to(dev), 256)
@@ -64,7 +64,6 @@ for c2, r in ((1024, 32), (512, 64), (256, 128)):
 
     ref = None
     for v in FWD:
-        os.environ["T2H_CELLSUMS_V2"] = v.rstrip("o")
         use_order[0] = v.endswith("o")
         planes[0].fill_(float("nan")); planes[1].fill_(float("nan")); bits.fill_(-1)
         fwd()
@@ -76,7 +75,6 @@ for c2, r in ((1024, 32), (512, 64), (256, 128)):
         med, best = timed(fwd)
         print(f"fwd  C={c2:5d} r={r:4d} variant={v}: {med:7.1f} us (min {best:6.1f})  {fwd_bytes / med / 1e6:6.2f} TB/s  "
               f"frac {fwd_bytes / med / 1e6 / 8:.3f}  identical={same}", flush=True)
-    os.environ.pop("T2H_CELLSUMS_V2", None)
 
     grads = [(torch.randn_like(p), l) for l, p in planes.items()]
     arr, lvs, lds = deferred._plane_args(grads)

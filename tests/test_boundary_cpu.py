@@ -40,6 +40,22 @@ def test_host_side_helpers_need_no_gpu():
     assert b"null pointer" in lib.t2h_last_error_string()
 
 
+def test_on_chip_cell_sums_refuse_the_one_pixel_level():
+    """t2h_sample_relu_cellsums*: level == nbits (a 1 x 1 plane) is an argument error, refused before any launch -- the on-chip
+    pass has no form for it (the deferred level takes t2h_sample_fwd_relu + t2h_segsum_fwd there)."""
+    import numpy as np
+    from tomosar2height_amd import _lib
+    lib = _lib.load()
+    buf = np.zeros(4096, np.float32)                      # host memory: valid-looking, 16-byte aligned, never launched on
+    p = buf.ctypes.data + (-buf.ctypes.data % 16)
+    nbits = 8
+    args = (p, p, 3, p, 1, 10, nbits, nbits, 0, 256, p, 256)
+    for name, tail in (("t2h_sample_relu_cellsums", (None, None)), ("t2h_sample_relu_cellsums2", (None, 0, None, None)),
+                       ("t2h_sample_relu_cellsums_ordered", (None, 0, None, None, None))):
+        assert getattr(lib, name)(*args, *tail) == -1, name
+        assert b"level < nbits" in lib.t2h_last_error_string(), name
+
+
 def test_grid_conv_dispatch_host_logic():
     """grid.py's routing (host logic, no launches): which convolutions the implicit-GEMM kernels accept, workspace
     plans of the C side, and that geometry outside them is left to the stock module."""

@@ -243,9 +243,10 @@ def test_on_chip_hidden_activations_equal_the_two_kernel_form(c, r, sum_level, d
 def test_cell_order_is_longest_first_and_changes_no_bit(c, r, sum_level, batch):
     """t2h_cell_order_build: the level's cells, then its 2 x 2 blocks of cells, each a permutation by FALLING row count; the
     on-chip walks launched with it (dense cells' workgroups first) give the bits of the launch without it -- forward (per-cell
-    sums, pooled sums, sign words), backward (dQ) -- and both forms of the r05 forward (a cell shared by four waves / a
-    2 x 2 block of cells per workgroup) give the bits of the r04 kernel."""
-    import os
+    sums, pooled sums, sign words), backward (dQ).  The forward against the two-kernel form (t2h_sample_fwd_relu ->
+    t2h_segsum_fwd -> t2h_plane_sumpool2x2): the sign words bit for bit, the sums bit for bit wherever the per-cell sum kernel
+    sums a cell's rows in sequence (t2h_segmean_workspace_bytes == 0).  The cases take both forms of the forward: K = 0 (a cell
+    shared by four waves: (1024, 32, 0), (512, 64, 0)) and K = 1 (a 2 x 2 block of cells per workgroup: the other three)."""
     from tomosar2height_amd import _lib, deferred
     tile = _tile(n=150000 if r == 128 else 90000, batch=batch)
     lv = tile.level(r)
@@ -264,24 +265,37 @@ def test_cell_order_is_longest_first_and_changes_no_bit(c, r, sum_level, batch):
     q = torch.randn(tile.B, r, r, c, generator=g).to(_dev())
     rs = 256 >> sum_level
 
-    def forward(order_arg, variant):
-        os.environ["T2H_CELLSUMS_V2"] = variant
-        try:
-            sums = torch.full((tile.B * rs * rs, c), 3.0, device=_dev())
-            pooled = torch.full((tile.B * (rs // 2) ** 2, c), 5.0, device=_dev())
-            bits = torch.zeros(tile.n_points * (c // 256) * 4, dtype=torch.int64, device=_dev())
-            _lib.call("t2h_sample_relu_cellsums_ordered", _lib.ptr(q), _lib.ptr(tile.pts), tile.dim, _lib.ptr(tile.off0), tile.B,
-                      tile.N, tile.nbits, lv, sum_level, c, _lib.ptr(sums), c, _lib.ptr(pooled) if sum_level < lv else None, c,
-                      _lib.ptr(bits), None if order_arg is None else _lib.ptr(order_arg), _lib.stream())
-            return sums, pooled, bits
-        finally:
-            os.environ.pop("T2H_CELLSUMS_V2", None)
+    def forward(order_arg):
+        sums = torch.full((tile.B * rs * rs, c), 3.0, device=_dev())
+        pooled = torch.full((tile.B * (rs // 2) ** 2, c), 5.0, device=_dev())
+        bits = torch.zeros(tile.n_points * (c // 256) * 4, dtype=torch.int64, device=_dev())
+        _lib.call("t2h_sample_relu_cellsums_ordered", _lib.ptr(q), _lib.ptr(tile.pts), tile.dim, _lib.ptr(tile.off0), tile.B,
+                  tile.N, tile.nbits, lv, sum_level, c, _lib.ptr(sums), c, _lib.ptr(pooled) if sum_level < lv else None, c,
+                  _lib.ptr(bits), None if order_arg is None else _lib.ptr(order_arg), _lib.stream())
+        return sums, pooled, bits
 
-    ref = forward(None, "0")                                     # the r04 kernel (one wave per chunk, its own neighbourhood)
-    for variant in ("1", "2"):                                   # r05: shared by four waves / 2 x 2 blocks of cells
-        for o in (None, order):
-            got = forward(o, variant)
-            assert all(torch.equal(a, b) for a, b in zip(ref, got)), (variant, o is not None)
+    ref = forward(None)
+    got = forward(order)
+    assert all(torch.equal(a, b) for a, b in zip(ref, got))
+    # the two-kernel form: hidden activations with their sign words, per-cell sums of the rows, 2 x 2 pooling of those sums
+    h = torch.empty(tile.n_points, c, device=_dev())
+    bits_ref = torch.zeros(tile.n_points * (c // 256) * 4, dtype=torch.int64, device=_dev())
+    _lib.call("t2h_sample_fwd_relu", _lib.ptr(q), _lib.ptr(tile.pts), tile.dim, tile.B, tile.N, r, c, _lib.ptr(h),
+              _lib.ptr(bits_ref), _lib.stream())
+    assert torch.equal(ref[2], bits_ref)
+    want = torch.full((tile.B * rs * rs, c), 3.0, device=_dev())
+    deferred._segsum_into(tile, h, sum_level, want)
+    ws_sum = _lib.load().t2h_segmean_workspace_bytes(tile.B, tile.N, tile.nbits, sum_level, c)
+    print(f"C={c} r={r} sum_level={sum_level} B={batch}: segmean workspace {ws_sum} bytes, "
+          f"sums {((ref[0] - want).abs().max() / want.abs().max()).item():.3e} max-normalised vs the two-kernel form")
+    if ws_sum == 0:
+        assert torch.equal(ref[0], want)          # the two-kernel form sums a cell's rows in sequence too: same bits
+    else:                                         # ... unless it takes the per-(cell, split) partials there: same sums, re-associated
+        assert ((ref[0] - want).abs().max() / want.abs().max()).item() <= 2e-6
+    if sum_level < lv:
+        want2 = torch.full((tile.B * (rs // 2) ** 2, c), 5.0, device=_dev())
+        deferred._sumpool_into(tile, ref[0], sum_level, want2)   # the pooled sums == t2h_plane_sumpool2x2 of the finest: same bits
+        assert torch.equal(ref[1], want2)
     planes = [(torch.randn(tile.B * (256 >> l) ** 2, c, generator=g).to(_dev()), l) for l in range(lv + 1)]
     arr, lvs, lds = deferred._plane_args(planes)
     ws_bytes = _lib.load().t2h_sample_bwd_workspace_bytes(tile.B, tile.N, tile.nbits, lv, c)

@@ -20,10 +20,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 GROUPS = {
     "default": {},
-    # the on-chip walks: r04 kernel, Morton dispatch order, matrix-core partials instead of the walk, no cell table
-    "walks_r04": {"T2H_CELLSUMS_V2": "0", "T2H_CELL_ORDER": "0", "T2H_CELLS_WALK": "0", "T2H_CELLS_TABLE": "0"},
-    "walks_blocks": {"T2H_CELLSUMS_V2": "2", "T2H_CELLS_WALK": "3", "T2H_CELLSUMS_V2_WGS": "1024", "T2H_ON_CHIP_MIN_WGS": "1024",
-                     "T2H_CELLS_MIN_WGS": "1024"},
+    # the on-chip walks: no cell table in the matrix-core partials; fewer workgroups for the per-cell partials
+    "walks_r04": {"T2H_CELLS_TABLE": "0"},
+    "walks_blocks": {"T2H_CELLS_MIN_WGS": "1024"},
     # the hidden activations written out / kept / two-pass backward; the VALU partials
     "hidden_in_memory": {"T2H_ON_CHIP_HIDDEN": "0", "T2H_SIGN_BITS": "0", "T2H_FUSED_SAMPLE_BWD": "0"},
     "partials_valu": {"T2H_CELLS_MFMA": "0", "T2H_SAMPLE_ADJOINT": "0", "T2H_ON_CHIP_MIN_PTS": "2"},
@@ -54,7 +53,6 @@ GROUPS = {
     "trunk_one_launch_strided": {"T2H_TRUNK_FUSED": "1", "T2H_TRUNK_UNIT_BOUNDS": "0", "T2H_TRUNK_FUSED_STRIDE": "112"},
     "trainer_tile_by_tile": {"T2H_COALESCE_TILES": "1"},
     "trainer_coalesce_two_unpipelined": {"T2H_COALESCE_TILES": "2", "T2H_PIPELINE_MICRO_BATCHES": "0"},
-    "trunk_loader0": {"T2H_TRUNK_LOADER": "0"},
     "point_first": {"T2H_GRID_FIRST_MIN_RATIO": "1000000"},
     "no_deferred": {"T2H_DEFER_MIN_CHANNELS": "0", "T2H_SAMPLE_ADJOINT_MAX_ROWS": "0"},
     "deferred_wide_only": {"T2H_DEFER_MIN_CHANNELS": "512", "T2H_SAMPLE_ADJOINT_MAX_ROWS": "64"},

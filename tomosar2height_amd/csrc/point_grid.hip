@@ -616,133 +616,14 @@ __device__ inline unsigned long long readlane_u64(unsigned long long v, int i) {
     return ((unsigned long long)hi << 32) | lo;
 }
 
-// Hidden activations that never leave the chip (t2h_sample_relu_cellsums): for a coarse sampling level (many points per cell)
-// one WAVE owns (cell of the sampling level, 256-channel chunk).  It stages the 3 x 3 pixel neighbourhood of the cell -- every
-// tap of every point of the cell lies in it -- in LDS once (9 KB), then walks the cell's rows child by child (children = the
-// cells of the finest resolution the sums are needed at, contiguous row runs in Morton order): per row the taps, four LDS
-// reads, the same multiply-add chain as sample_fwd_kernel, ReLU, four ballots for the packed sign bits, and the running
-// per-child sum in registers, written when the child ends (empty children write zeros, so nothing is memset).  Out go the
-// per-cell sums (half the size of h at two points per finest cell) and 1 bit per element; h [N, C] itself is never written
-// or re-read.  Same bits as t2h_sample_fwd_relu + t2h_segsum_fwd: identical operation order per element and per sum.
-__global__ __launch_bounds__(256) void sample_relu_cellsums_kernel(const float *__restrict__ plane,
-                                                                 const float *__restrict__ pts, int dim,
-                                                                 const int32_t *__restrict__ off0, int nbits, int level,
-                                                                 int sum_level, int C, float *__restrict__ sums, int ld_sums,
-                                                                 unsigned long long *__restrict__ bits, int npts_m1,
-                                                                 float *__restrict__ sums2, int ld_sums2) {
-    extern __shared__ float nb_lds[];                                   // [waves][9][256]
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int chunk = blockIdx.y * 4 + wave;
-    if (chunk * 256 >= C) return;                                       // (no workgroup barrier below)
-    float *T = nb_lds + wave * (9 * 256);
-    const int rbits = nbits - level, r = 1 << rbits;
-    const int64_t cellrow = blockIdx.x;
-    const int b = (int)(cellrow >> (2 * rbits));
-    const uint32_t mk = (uint32_t)(cellrow & (((int64_t)1 << (2 * rbits)) - 1));
-    const int cx = (int)compact1by1(mk), cy = (int)compact1by1(mk >> 1);
-    const int c0 = chunk * 256 + lane * 4;
-#pragma unroll
-    for (int sl = 0; sl < 9; ++sl) {
-        const int py = cy - 1 + sl / 3, px = cx - 1 + sl % 3;
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if ((unsigned)py < (unsigned)r && (unsigned)px < (unsigned)r)
-            v = *reinterpret_cast<const float4 *>(plane + (((size_t)b * r + py) * r + px) * C + c0);
-        *reinterpret_cast<float4 *>(T + sl * 256 + lane * 4) = v;
-    }
-    const int d = level - sum_level, nchild = 1 << (2 * d), rs = 1 << (nbits - sum_level);
-    const size_t obase = ((size_t)b << (2 * nbits)) + ((size_t)mk << (2 * level));
-    const int cpc = C >> 8;                                             // 256-channel chunks per row (bit words)
-    // the taps of 64 consecutive rows are computed lane-parallel (lane l = row nb0 + l) and handed to the row loop by
-    // readlane: ~40 instructions once per 64 rows instead of once per row and lane.  A tap outside the plane gets weight 0 and
-    // reads the staged zero (the sample kernel skips it: the same value)
-    int nb0 = 0, slot_l = 0;
-    float nw_l = 0.f, ne_l = 0.f, sw_l = 0.f, se_l = 0.f;
-    bool have = false;
-    float4 pe = make_float4(0.f, 0.f, 0.f, 0.f), p01 = pe;             // pooled-output state of the current quad of children
-    // blockIdx.z: this workgroup's share of the children (dense cells would otherwise set the kernel's duration: one wave
-    // walking 500+ rows while most of the chip has finished); the children's sums are independent, so nothing is reduced
-    const int per_group = nchild / (int)gridDim.z, child_lo = (int)blockIdx.z * per_group, child_hi = child_lo + per_group;
-    for (int cb = child_lo; cb < child_hi; cb += 64) {                  // children in batches of 64: their row boundaries
-        const int ci = cb + lane;
-        const int bnd_lo = ci <= child_hi ? off0[obase + ((size_t)ci << (2 * sum_level))] : 0;
-        const int bnd_hi = ci + 1 <= child_hi ? off0[obase + ((size_t)(ci + 1) << (2 * sum_level))] : 0;
-        const int nc = min(64, child_hi - cb);
-        for (int c = 0; c < nc; ++c) {
-            const int s = __builtin_amdgcn_readlane(bnd_lo, c), e = __builtin_amdgcn_readlane(bnd_hi, c);
-            float4 sum = make_float4(0.f, 0.f, 0.f, 0.f);
-            int n = s;
-            while (n < e) {
-                if (!have || n >= nb0 + 64) {
-                    nb0 = n; have = true;
-                    const int nn = min(n + lane, npts_m1);                // rows past this cell belong to later cells: valid
-                    const Taps tp = make_taps(pts[(size_t)nn * dim + 0], pts[(size_t)nn * dim + 1], r);
-                    const float fx1 = (float)min(max(r - 1 - tp.x0, 0), 1), fy1 = (float)min(max(r - 1 - tp.y0, 0), 1);
-                    nw_l = __fmul_rn(tp.wx0, tp.wy0);
-                    ne_l = __fmul_rn(__fmul_rn(tp.wx1, tp.wy0), fx1);      // (no compare -> mask -> select here: see the v2 kernel)
-                    sw_l = __fmul_rn(__fmul_rn(tp.wx0, tp.wy1), fy1);
-                    se_l = __fmul_rn(__fmul_rn(tp.wx1, tp.wy1), __fmul_rn(fx1, fy1));
-                    slot_l = min(max(tp.y0 - cy + 1, 0), 1) * 3 + min(max(tp.x0 - cx + 1, 0), 1);     // 0 or 1 each by construction
-                }
-                const int i0 = n - nb0, cnt = min(e - n, 64 - i0);        // rows of this child inside the current batch
-                auto row = [&](int i, int nrow) -> float4 {
-                    const float nw = readlane_f(nw_l, i), ne = readlane_f(ne_l, i), sw = readlane_f(sw_l, i), se = readlane_f(se_l, i);
-                    const float *t00 = T + __builtin_amdgcn_readlane(slot_l, i) * 256 + lane * 4;
-                    const float4 v00 = *reinterpret_cast<const float4 *>(t00), v01 = *reinterpret_cast<const float4 *>(t00 + 256);
-                    const float4 v10 = *reinterpret_cast<const float4 *>(t00 + 3 * 256), v11 = *reinterpret_cast<const float4 *>(t00 + 4 * 256);
-                    float4 a;
-                    a.x = __fmul_rn(v00.x, nw); a.y = __fmul_rn(v00.y, nw); a.z = __fmul_rn(v00.z, nw); a.w = __fmul_rn(v00.w, nw);
-                    a.x = __fadd_rn(a.x, __fmul_rn(v01.x, ne)); a.y = __fadd_rn(a.y, __fmul_rn(v01.y, ne));
-                    a.z = __fadd_rn(a.z, __fmul_rn(v01.z, ne)); a.w = __fadd_rn(a.w, __fmul_rn(v01.w, ne));
-                    a.x = __fadd_rn(a.x, __fmul_rn(v10.x, sw)); a.y = __fadd_rn(a.y, __fmul_rn(v10.y, sw));
-                    a.z = __fadd_rn(a.z, __fmul_rn(v10.z, sw)); a.w = __fadd_rn(a.w, __fmul_rn(v10.w, sw));
-                    a.x = __fadd_rn(a.x, __fmul_rn(v11.x, se)); a.y = __fadd_rn(a.y, __fmul_rn(v11.y, se));
-                    a.z = __fadd_rn(a.z, __fmul_rn(v11.z, se)); a.w = __fadd_rn(a.w, __fmul_rn(v11.w, se));
-                    a.x = fmaxf(a.x, 0.f); a.y = fmaxf(a.y, 0.f); a.z = fmaxf(a.z, 0.f); a.w = fmaxf(a.w, 0.f);
-                    const unsigned long long w0 = __ballot(a.x > 0.f), w1 = __ballot(a.y > 0.f);
-                    const unsigned long long w2 = __ballot(a.z > 0.f), w3 = __ballot(a.w > 0.f);
-                    if (lane == 0 && bits) {                              // (null under no_grad: nothing will read the signs)
-                        unsigned long long *dst = bits + ((size_t)chunk * ((size_t)npts_m1 + 1) + nrow) * 4;
-                        dst[0] = w0; dst[1] = w1; dst[2] = w2; dst[3] = w3;
-                    }
-                    return a;
-                };
-                int j = 0;
-                for (; j + 1 < cnt; j += 2) {                             // two rows in flight; summed in row order
-                    const float4 a0 = row(i0 + j, n + j), a1 = row(i0 + j + 1, n + j + 1);
-                    sum.x += a0.x; sum.y += a0.y; sum.z += a0.z; sum.w += a0.w;
-                    sum.x += a1.x; sum.y += a1.y; sum.z += a1.z; sum.w += a1.w;
-                }
-                if (j < cnt) {
-                    const float4 a0 = row(i0 + j, n + j);
-                    sum.x += a0.x; sum.y += a0.y; sum.z += a0.z; sum.w += a0.w;
-                }
-                n += cnt;
-            }
-            const uint32_t cm = (uint32_t)(cb + c);                      // child's Morton code inside the cell
-            const int fx = (cx << d) + (int)compact1by1(cm), fy = (cy << d) + (int)compact1by1(cm >> 1);
-            *reinterpret_cast<float4 *>(sums + (((size_t)b * rs + fy) * rs + fx) * ld_sums + c0) = sum;
-            if (sums2) {
-                // the 2 x 2 pooled sums one level up, formed from the four children while they are in registers (children are
-                // visited in Morton order = the order (c0 + c1) + (c2 + c3) of plane_sumpool2x2_kernel: same bits)
-                const unsigned k4 = cm & 3u;
-                if (k4 == 0u) pe = sum;
-                else if (k4 == 1u) p01 = make_float4(pe.x + sum.x, pe.y + sum.y, pe.z + sum.z, pe.w + sum.w);
-                else if (k4 == 2u) pe = sum;
-                else {
-                    const float4 o = make_float4(p01.x + (pe.x + sum.x), p01.y + (pe.y + sum.y), p01.z + (pe.z + sum.z),
-                                                 p01.w + (pe.w + sum.w));
-                    const int rs2 = rs >> 1;
-                    *reinterpret_cast<float4 *>(sums2 + (((size_t)b * rs2 + (fy >> 1)) * rs2 + (fx >> 1)) * ld_sums2 + c0) = o;
-                }
-            }
-        }
-    }
-}
-
-// ---- r05: the same pass with the neighbourhood SHARED by the workgroup's four waves ----------------------------------------
-// sample_relu_cellsums_kernel gives every wave its own 9 KB neighbourhood (one wave per 256-channel chunk): 36 KB of LDS per
-// workgroup = 4 waves per SIMD, a 9 KB L2 -> LDS round trip in front of every wave's ~16 rows, ~75 vector instructions per row
-// (the compiler pairs (v00.x nw, v01.x ne) for its packed multiplies and shuffles registers to do so).  Here a workgroup is
+// ---- hidden activations that never leave the chip (t2h_sample_relu_cellsums) -----------------------------------------------
+// For a coarse sampling level (many points per cell): the 3 x 3 pixel neighbourhood of a sampling cell -- every tap of every
+// point of the cell lies in it -- is staged in LDS once, then the cell's rows are walked child by child (children = the cells
+// of the finest resolution the sums are needed at, contiguous row runs in Morton order): per row the taps, ReLU, the packed
+// sign bits, and the running per-child sum in registers, written when the child ends (empty children write zeros, so nothing
+// is memset).  h [N, C] itself is never written or re-read.  Same bits as t2h_sample_fwd_relu + t2h_segsum_fwd: identical
+// operation order per element and per sum.  The neighbourhood is SHARED by the workgroup's four waves (r05; the r04 form gave
+// every wave its own 9 KB copy: 4 waves per SIMD, ~75 vector instructions per row).  A workgroup is
 //   K = 0: ONE sampling cell x ONE 256-channel chunk: the 3 x 3 neighbourhood staged once (9 KB), each wave a quarter of the
 //          workgroup's children (blockIdx.z splits them further);
 //   K = 1: a 2 x 2 BLOCK of sampling cells, one per wave, sharing its 4 x 4 neighbourhood (16 KB) -- levels with few rows
@@ -1544,7 +1425,7 @@ __global__ __launch_bounds__(kCellThreads) void sample_bwd_cells_mfma_kernel(con
     }
 }
 
-// ---- t2h_sample_bwd_from_sums with packed sign bits: the backward twin of sample_relu_cellsums_kernel -----------------------
+// ---- t2h_sample_bwd_from_sums with packed sign bits: the backward twin of sample_relu_cellsums_v2_kernel --------------------
 // One WAVE walks a contiguous run of the finest cells ("children", level wl) of ONE sampling cell for a 256-channel chunk,
 // lane l = channels 4 l .. 4 l + 3.  Per child the gathered gradient G = sum_q plane_q[parent_q(child)] is formed once (all
 // rows of a child share it; the next child's plane rows are requested while this child's rows run); per row the four tap
@@ -2190,39 +2071,29 @@ T2H_API int t2h_sample_relu_cellsums_ordered(const float *plane_nhwc, const floa
         ((uintptr_t)plane_nhwc & 15) || ((uintptr_t)sums_nhwc & 15) || ((uintptr_t)sign_bits & 15))
         return fail(T2H_ERR_ARG, "sample_relu_cellsums: needs C %% 256 == 0, sum_level <= level, 16-byte aligned rows");
     if (rows_of(B, N) == 0) return fail(T2H_ERR_ARG, "sample_relu_cellsums: empty tile");
+    // K = 1 stages a 2 x 2 block of sampling cells: the 1 x 1 plane of level == nbits has none (t2h_cell_order_len is 0 there)
+    if (level == nbits)
+        return fail(T2H_ERR_ARG, "sample_relu_cellsums: needs level < nbits (a 1 x 1 plane: use t2h_sample_fwd_relu + t2h_segsum_fwd)");
     const int64_t cells = (int64_t)B << (2 * (nbits - level));
-    const int chunks = C / 256, waves = chunks < 4 ? chunks : 4;
-    int groups = 1;                                                   // split the children until ~8192 workgroups exist (4096: +10 us at r = 64; 16384: +18 us at r = 32)
+    const int chunks = C / 256;
     const int nchild = 1 << (2 * (level - sum_level));
-    static const int min_wgs = [] { const char* e = getenv("T2H_ON_CHIP_MIN_WGS"); return e ? atoi(e) : 8192; }();
-    // r05: the workgroup shares one staged neighbourhood (sample_relu_cellsums_v2_kernel); T2H_CELLSUMS_V2=0: the r04 kernel (A/B)
-    const char *e_v2 = getenv("T2H_CELLSUMS_V2"), *e_wgs = getenv("T2H_CELLSUMS_V2_WGS");        // (read per call: the probes flip them)
-    const int v2 = e_v2 ? atoi(e_v2) : 1, v2_wgs = e_wgs ? atoi(e_wgs) : 8192;
-    if (v2 && nbits - level >= 1) {
-        const int npts_m1 = (int)(rows_of(B, N) - 1);
-        unsigned long long *bw = static_cast<unsigned long long *>(sign_bits);
-        const int quad = pooled_nhwc ? 4 : 1;                         // children a wave must hold (whole quads for the pooled sums)
-        note_kernel("t2h::sample_relu_cellsums_v2_kernel");
-        const bool k0 = v2 != 2 && nchild >= 4 * quad;              // K = 0: the four waves share out the cell's children
-        // cell_order: [cells] the level's cells, then [cells / 4] its 2 x 2 blocks, each by falling row count
-        const int32_t *order_k0 = cell_order, *order_k1 = cell_order ? cell_order + cells : nullptr;
-        int gz = 1;
-        if (k0) while (nchild / (4 * gz * 2) >= quad && cells * chunks * gz < v2_wgs) gz *= 2;
-        const dim3 grid((unsigned)((k0 ? cells : (cells >> 2)) * chunks * gz));           // K = 1: a 2 x 2 block of cells per workgroup
+    constexpr int64_t kMinWgs = 8192;                                 // split the children until ~8192 workgroups exist
+    const int npts_m1 = (int)(rows_of(B, N) - 1);
+    unsigned long long *bw = static_cast<unsigned long long *>(sign_bits);
+    const int quad = pooled_nhwc ? 4 : 1;                             // children a wave must hold (whole quads for the pooled sums)
+    note_kernel("t2h::sample_relu_cellsums_v2_kernel");
+    const bool k0 = nchild >= 4 * quad;                               // K = 0: the four waves share out the cell's children
+    // cell_order: [cells] the level's cells, then [cells / 4] its 2 x 2 blocks, each by falling row count
+    const int32_t *order_k0 = cell_order, *order_k1 = cell_order ? cell_order + cells : nullptr;
+    int gz = 1;
+    if (k0) while (nchild / (4 * gz * 2) >= quad && cells * chunks * gz < kMinWgs) gz *= 2;
+    const dim3 grid((unsigned)((k0 ? cells : (cells >> 2)) * chunks * gz));               // K = 1: a 2 x 2 block of cells per workgroup
 #define T2H_V2_LAUNCH(KK, PP) hipLaunchKernelGGL((sample_relu_cellsums_v2_kernel<KK, PP>), grid, dim3(256), 0, as_stream(stream), \
-            plane_nhwc, pts, dim, off0, nbits, level, sum_level, C, sums_nhwc, ld_sums, bw, npts_m1, pooled_nhwc, ld_pooled, k0 ? order_k0 : order_k1, gz)
-        if (k0) { if (pooled_nhwc) T2H_V2_LAUNCH(0, true); else T2H_V2_LAUNCH(0, false); }
-        else { if (pooled_nhwc) T2H_V2_LAUNCH(1, true); else T2H_V2_LAUNCH(1, false); }
+        plane_nhwc, pts, dim, off0, nbits, level, sum_level, C, sums_nhwc, ld_sums, bw, npts_m1, pooled_nhwc, ld_pooled, k0 ? order_k0 : order_k1, gz)
+    if (k0) { if (pooled_nhwc) T2H_V2_LAUNCH(0, true); else T2H_V2_LAUNCH(0, false); }
+    else { if (pooled_nhwc) T2H_V2_LAUNCH(1, true); else T2H_V2_LAUNCH(1, false); }
 #undef T2H_V2_LAUNCH
-        return check_launch("sample_relu_cellsums(v2)");
-    }
-    // (with pooled sums a workgroup's share of the children must hold whole quads)
-    while (groups < (pooled_nhwc ? nchild / 4 : nchild) && cells * ((chunks + 3) / 4) * groups < min_wgs) groups *= 2;
-    hipLaunchKernelGGL(sample_relu_cellsums_kernel, dim3((unsigned)cells, (chunks + 3) / 4, groups), dim3(64 * waves),
-                       (size_t)waves * 9 * 256 * sizeof(float), as_stream(stream), plane_nhwc, pts, dim, off0, nbits, level,
-                       sum_level, C, sums_nhwc, ld_sums, static_cast<unsigned long long *>(sign_bits), (int)(rows_of(B, N) - 1),
-                       pooled_nhwc, ld_pooled);
-    return check_launch("sample_relu_cellsums");
+    return check_launch("sample_relu_cellsums(v2)");
 }
 
 T2H_API int t2h_sample_bwd_from_sums(const float *const *gplanes_nhwc, const int *levels, const int *lds, int n_planes,
@@ -2282,13 +2153,12 @@ T2H_API int t2h_sample_bwd_from_sums_ordered(const float *const *gplanes_nhwc, c
         const int64_t rows_per_wg = rows_of(B, N) / (groups * cp.S > 0 ? groups * cp.S : 1);
         if (folded > 0 && rows_per_wg * table_on >= entries) tlevel = tl;
     }
-    static const int walk_on = getenv("T2H_CELLS_WALK") ? atoi(getenv("T2H_CELLS_WALK")) : 1;
-    if (mask_is_bits && walk_on && level >= 1 && nbits - level >= 1 && n_planes <= kWalkPlanes) {
+    if (mask_is_bits && level >= 1 && nbits - level >= 1 && n_planes <= kWalkPlanes) {
         // walk level: the finest plane's cells, and at least one level below the sampling level (the waves split children)
         int wl = level - 1;
         for (int q = 0; q < n_planes; ++q) wl = levels[q] < wl ? levels[q] : wl;
-        // few rows per sampling cell: one workgroup per 2 x 2 block of cells (walk_on == 2 / 3 force one of the forms)
-        const bool blocks = walk_on == 3 || (walk_on == 1 && rows_of(B, N) < 64 * groups);
+        // few rows per sampling cell: one workgroup per 2 x 2 block of cells
+        const bool blocks = rows_of(B, N) < 64 * groups;
         const unsigned long long *bw = static_cast<const unsigned long long *>(mask);
         const int npts_m1 = (int)(rows_of(B, N) - 1);
         GroupCfg g = group_cfg<4>(C);

@@ -34,7 +34,6 @@ FUSED_SAMPLE_BWD = os.environ.get("T2H_FUSED_SAMPLE_BWD", "1") != "0"      # A/B
 CELLS_MFMA = os.environ.get("T2H_CELLS_MFMA", "1") != "0"                  # (mirrors the library's switch: the bit mask needs it)
 SIGN_BITS = os.environ.get("T2H_SIGN_BITS", "1") != "0"                    # A/B: 0 = keep the hidden activations for the mask
 ON_CHIP_HIDDEN = os.environ.get("T2H_ON_CHIP_HIDDEN", "1") != "0"          # A/B: 0 = sample kernel + per-cell sum kernel
-CELL_ORDER = os.environ.get("T2H_CELL_ORDER", "1") != "0"                  # A/B: 0 = the on-chip walks start their cells in Morton order
 ON_CHIP_MIN_PTS_PER_CELL = float(os.environ.get("T2H_ON_CHIP_MIN_PTS", "8"))   # the walk is sequential inside a cell
 
 
@@ -162,7 +161,8 @@ class _DeferredLevel(torch.autograd.Function):
         need_bwd = any(ctx.needs_input_grad[:4])
         bits_ok = (SIGN_BITS and c2 % 256 == 0 and FUSED_SAMPLE_BWD and CELLS_MFMA and tile.n_points > 0 and
                    _lib.ws_bytes("t2h_sample_bwd_workspace_bytes", tile.B, tile.N, tile.nbits, tile.level(r), c2) > 0)
-        on_chip = (bits_ok if need_bwd else (c2 % 256 == 0 and tile.n_points > 0)) and ON_CHIP_HIDDEN
+        # (the on-chip pass needs 2 x 2 blocks of sampling cells: not the 1 x 1 plane of level == nbits)
+        on_chip = (bits_ok if need_bwd else (c2 % 256 == 0 and tile.n_points > 0)) and ON_CHIP_HIDDEN and tile.level(r) < tile.nbits
         if on_chip and tile.n_points >= ON_CHIP_MIN_PTS_PER_CELL * tile.B * r * r:
             # coarse sampling level: interpolation, ReLU, sign bits and the per-cell sums of the finest needed resolution in one
             # pass over the cells -- the hidden activations are never written to memory (t2h_sample_relu_cellsums)
@@ -176,7 +176,7 @@ class _DeferredLevel(torch.autograd.Function):
             second = None
             if len(levels) > 1 and levels[1] == levels[0] + 1 and levels[0] < tile.level(r):
                 second = state._matrix(state.S, levels[1])[:, lo:hi]
-            order = tile.cell_order(tile.level(r)) if CELL_ORDER else None
+            order = tile.cell_order(tile.level(r))
             _lib.call("t2h_sample_relu_cellsums_ordered", _lib.ptr(q_rows), _lib.ptr(tile.pts), tile.dim, _lib.ptr(tile.off0), tile.B,
                       tile.N, tile.nbits, tile.level(r), levels[0], c2, finest.data_ptr(), finest.stride(0),
                       None if second is None else second.data_ptr(), 0 if second is None else second.stride(0),
@@ -447,7 +447,7 @@ class Deferred:
             arr, lvs, lds = _plane_args(planes)
             ws = _lib.workspace(ws_bytes, h.device)
             dq = torch.empty(tile.B * r * r, c2, dtype=torch.float32, device=h.device)
-            order = tile.cell_order(level) if (CELL_ORDER and mask_is_bits) else None
+            order = tile.cell_order(level) if mask_is_bits else None
             _lib.call("t2h_sample_bwd_from_sums_ordered", arr, lvs, lds, len(planes), _lib.ptr(tile.cell), _lib.ptr(h),
                       1 if mask_is_bits else 0, _lib.ptr(tile.pts), tile.dim, _lib.ptr(tile.off0), tile.B, tile.N, tile.nbits,
                       level, c2, _lib.ptr(dq), _lib.ptr(ws), ws_bytes, None if order is None else _lib.ptr(order), _lib.stream(),

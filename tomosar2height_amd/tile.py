@@ -197,7 +197,7 @@ class TileIndex:
                 tile.sample_adjoint(0)
             for lv in range(min(4, tile.nbits)):
                 deferred.counts(tile, lv)
-                if lv >= 1 and deferred.CELL_ORDER:
+                if lv >= 1:
                     tile.cell_order(lv)
             tile.ready = torch.cuda.Event()
             tile.ready.record(stream)
