@@ -297,6 +297,7 @@ __global__ __launch_bounds__(NT, 2) void bx3_rows_kernel(RowsArgs p) {
     static_assert(!PERSIST || (NTAP == 1 && UPM == 0 && T2H_BX3_BDIRECT != 0), "PERSIST: plain 1-tap form with register-fetched weights");
     constexpr int PXB = CCH * 2 + 16;     // bytes per pixel and plane of the halo image: CCH bf16 + 16 B (an odd multiple of 16 B)
     constexpr int NQ = CCH / 16, F4 = CCH / 4, NSTEP = NTAP * NQ;
+    constexpr int QUNROLL = (NPL == 3 && NTAP == 9) ? 1 : NQ;            // (the piecewise three-way 3 x 3 path keeps its 16-channel steps apart)
     constexpr int TM = TH / WAVES_M, TN = BN / (32 * WAVES_N);
     constexpr int HB = NTAP == 9 ? 1 : 0;                                // halo border
     constexpr int HW = TW + 2 * HB;                                      // pixels per staged image row
@@ -473,13 +474,14 @@ __global__ __launch_bounds__(NT, 2) void bx3_rows_kernel(RowsArgs p) {
 #pragma unroll 1
         for (int tap = 0; tap < NTAP; ++tap) {
             const int ky = NTAP == 9 ? tap / 3 : 0, kx = NTAP == 9 ? tap - 3 * ky : 0;
-#pragma unroll
+#pragma unroll QUNROLL
             for (int q = 0; q < NQ; ++q, ++s) {
                 const unsigned char *cur = bbuf + (s & 1) * BSLAB;
                 const int st = tap * NQ + q;
                 uint4 af[TM][NPL], bfr[TN][NPL];
+                constexpr bool PIECEWISE = NPL == 3 && NTAP == 9;        // (reads its A fragments one tile row at a time, below)
 #pragma unroll
-                for (int i = 0; i < TM; ++i) {
+                for (int i = 0; i < (PIECEWISE ? 0 : TM); ++i) {
                     const int px = (wm * TM + i + ky) * HW + r + kx;
                     const unsigned char *a = halo + px * PXB + q * 32 + h * 16;
 #pragma unroll
@@ -521,6 +523,34 @@ __global__ __launch_bounds__(NT, 2) void bx3_rows_kernel(RowsArgs p) {
                                 acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(*reinterpret_cast<f16x8 *>(&af[i][ia[e]]),
                                                                                     *reinterpret_cast<f16x8 *>(&bfr[j][ib[e]]), acc[i][j], 0, 0, 0);
                     if (st + 1 == NSTEP && c + 1 < c_end) publish_block_max((c + 1) & 1);      // (under the MFMAs; the barrier below publishes)
+                } else if (PIECEWISE) {
+                    // The 3 x 3 form of the three-way split.  The six piece products of a step are summed in a fresh accumulator
+                    // (smallest first, the leading product last) and joined to the running sum by ONE fp32 addition: every MFMA rounds
+                    // its whole accumulator, and six roundings per step at the size of the running sum took reductions of 9 * 128 and
+                    // more terms to 4.3 .. 5.6e-7 of sum |a b| (tests/test_launch_census.py), where the piece sums are 2^-8 and less of
+                    // it.  The A fragments are read one tile row at a time, so that the 16 registers of the piece accumulator replace
+                    // the fragments of the other rows instead of adding to them.  (The 1-tap products reduce 64 .. 512 terms and keep
+                    // the plain chain, as does bx3_wgrad_kernel.)
+#pragma unroll
+                    for (int i = 0; i < TM; ++i) {
+                        const unsigned char *a = halo + ((wm * TM + i + ky) * HW + r + kx) * PXB + q * 32 + h * 16;
+                        uint4 ar[NPL];
+#pragma unroll
+                        for (int pl = 0; pl < NPL; ++pl) ar[pl] = *reinterpret_cast<const uint4 *>(a + pl * PLANE);
+#pragma unroll
+                        for (int j = 0; j < TN; ++j) {
+                            f32x16 part;
+#pragma unroll
+                            for (int z = 0; z < 16; ++z) part[z] = 0.0f;
+#pragma unroll
+                            for (int e = 0; e < 6; ++e)
+                                part = __builtin_amdgcn_mfma_f32_32x32x16_bf16(*reinterpret_cast<bf16x8 *>(&ar[ia[e]]),
+                                                                                *reinterpret_cast<bf16x8 *>(&bfr[j][ib[e]]), part, 0, 0, 0);
+#pragma unroll
+                            for (int z = 0; z < 16; ++z) acc[i][j][z] += part[z];
+                            __builtin_amdgcn_sched_barrier(0);           // (keeps the tiles apart: one piece accumulator alive at a time)
+                        }
+                    }
                 } else {
 #pragma unroll
                     for (int e = (NPL == 3 ? 0 : 5); e < 6; ++e)
