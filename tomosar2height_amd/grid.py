@@ -14,6 +14,7 @@ runs in channels_last mode and otherwise keep the plain torch composition.
 import ctypes
 import contextlib
 import os
+import weakref
 
 import torch
 import torch.nn.functional as F
@@ -158,95 +159,82 @@ def _h2() -> bool:
     return CONV_PRECISION == "f16x2"
 
 
+# the kinds of prepared buffer (SplitWeightCache): a 3x3 weight forward / transposed, a weight matrix read as [K,N] / [N,K], a
+# transposed-convolution weight as the matrix [K,N] / [N,K]; each in the bf16 planes or (T2H_F16X2) the fp16 two-plane form
+_CONV_FWD, _CONV_T, _MAT_KN, _MAT_NK, _UP_KN, _UP_NK = range(6)
+# (matrix form?, fp16 two-plane buffers?) -> (byte-size query, single-call prepare, algorithmic bytes per weight element)
+_SPLIT_ENTRIES = {(False, False): ("t2h_conv3x3_bx3_weights_bytes", "t2h_conv3x3_bx3_prepare", 10),
+                  (False, True): ("t2h_conv3x3_f16x2_weights_bytes", "t2h_conv3x3_f16x2_prepare", 12),
+                  (True, False): ("t2h_gemm_bx3_weights_bytes", "t2h_gemm_bx3_prepare", 10),
+                  (True, True): ("t2h_gemm_f16x2_weights_bytes", "t2h_gemm_f16x2_prepare", 12)}
+
+
+def _split_desc(kind: int, w: torch.Tensor):
+    """What the single prepare, the byte-size query and ``t2h_split_weights_batch`` need to know about the weight behind a buffer of
+    ``kind``: (``t2h_prep_desc`` kind, a, b, ldw, whether the batch can read the weight as it lies).  Descriptor kinds 0 / 1: the
+    3x3 weight [Cout,Cin,3,3] forward / transposed (a = Cin, b = Cout); 2 / 3: a matrix read as [K,N] / [N,K] (a = K, b = N, ldw =
+    its row stride) -- a plain one, or a ConvTranspose2d(2, stride 2) weight [Cin,Cout,2,2], whose memory [Cin][2][2][Cout] IS the
+    matrix [Cin][4 Cout]."""
+    if kind <= _CONV_T:
+        return kind, w.shape[1], w.shape[0], 0, w.permute(0, 2, 3, 1).is_contiguous()
+    if kind >= _UP_KN:
+        cin, n4 = w.shape[0], 4 * w.shape[1]
+        return (2, cin, n4, n4, True) if kind == _UP_KN else (3, n4, cin, n4, True)
+    batchable = w.dim() == 2 and w.stride(1) == 1
+    return (2, w.shape[0], w.shape[1], w.stride(0), batchable) if kind == _MAT_KN else (3, w.shape[1], w.shape[0], w.stride(0), batchable)
+
+
+class _SplitEntry:
+    __slots__ = ("ref", "version", "data_ptr", "buf", "maxslot", "ready")
+
+    def __init__(self, ref, buf):
+        self.ref, self.version, self.data_ptr, self.buf, self.maxslot, self.ready = ref, None, None, buf, 3, _lib.Ready()
+
+
 class SplitWeightCache:
-    """The three bf16 planes of a convolution weight in MFMA operand order (``t2h_conv3x3_bx3_prepare``): a function of the
-    weight alone, so computed when the weight changes (its version counter / storage moves: every optimizer, FlatAdamW included,
-    bumps the counter) instead of per tile.  The buffers are updated IN PLACE, so a captured hipGraph keeps reading current
-    values after ``refresh()`` (called by ``Trainer.optimizer_boundary``; a replayed graph runs no Python per tile)."""
+    """The split planes of a weight in MFMA operand order (three bf16 planes, or the fp16 two-plane buffers under 'f16x2'): a
+    function of the weight alone, so computed when the weight changes (its version counter / storage moves: every optimizer,
+    FlatAdamW included, bumps the counter) instead of per tile.  The buffers are updated IN PLACE, so a captured hipGraph keeps
+    reading current values after ``refresh()`` (called by ``Trainer.optimizer_boundary``; a replayed graph runs no Python per
+    tile).  One entry per (weight, kind, fp16 buffers?); ``_split_desc`` describes a kind to the single prepare and to the batch."""
 
     def __init__(self):
-        self.entries = {}          # (id(weight), transposed) -> [weakref, version, data_ptr, buffer, max slot, _lib.Ready]
+        self.entries = {}          # (id(weight), kind, fp16 two-plane?) -> _SplitEntry
 
     def get(self, w: torch.Tensor, transposed: bool) -> torch.Tensor:
-        import weakref
-        key = (id(w), ("h2t" if transposed else "h2f") if _h2() else bool(transposed))
-        e = self.entries.get(key)
-        cout, cin = w.shape[0], w.shape[1]
-        if e is None or e[0]() is not w:
-            lib = _lib.load()
-            nbytes = int((lib.t2h_conv3x3_f16x2_weights_bytes if _h2() else lib.t2h_conv3x3_bx3_weights_bytes)(cin, cout))
-            buf = torch.empty(nbytes, dtype=torch.uint8, device=w.device)
-            e = self.entries[key] = [weakref.ref(w, lambda _r, k=key: self.entries.pop(k, None)), None, None, buf, 3, _lib.Ready()]
-        if e[1] != w._version or e[2] != w.data_ptr():
-            self._prepare(w, key[1], e[3])
-            e[1], e[2], e[4] = w._version, w.data_ptr(), 3
-            e[5].mark()
-        else:
-            e[5].wait()                                       # (filled on another stream: that fill first)
-        return e[3]
-
-    @staticmethod
-    def _prepare(w, kind, buf):
-        cout, cin = w.shape[0], w.shape[1]
-        h2 = kind in ("h2t", "h2f")
-        transposed = kind in (True, "h2t")
-        _lib.call("t2h_conv3x3_f16x2_prepare" if h2 else "t2h_conv3x3_bx3_prepare", _lib.ptr(w), cin, cout, 1 if transposed else 0,
-                  _lib.ptr(buf), _lib.stream(), nbytes=(12 if h2 else 10) * w.numel())
+        """A 3x3 weight [Cout,Cin,3,3] in [Cout][3][3][Cin] memory, for the forward or (``transposed``) the data gradient."""
+        return self._get(w, _CONV_T if transposed else _CONV_FWD)
 
     def get_gemm(self, w: torch.Tensor, w_is_kn: bool) -> torch.Tensor:
         """The same for a plain weight matrix of the 1-tap (GEMM) form: ``w`` [N, K] (nn.Linear) or, ``w_is_kn``, [K, N]."""
-        import weakref
-        key = (id(w), ("kn" if w_is_kn else "nk") + ("_h2" if _h2() else ""))
-        e = self.entries.get(key)
-        k, n = (w.shape[0], w.shape[1]) if w_is_kn else (w.shape[1], w.shape[0])
-        if e is None or e[0]() is not w:
-            lib = _lib.load()
-            buf = torch.empty(int((lib.t2h_gemm_f16x2_weights_bytes if _h2() else lib.t2h_gemm_bx3_weights_bytes)(k, n)),
-                              dtype=torch.uint8, device=w.device)
-            e = self.entries[key] = [weakref.ref(w, lambda _r, kk=key: self.entries.pop(kk, None)), None, None, buf, 3, _lib.Ready()]
-        if e[1] != w._version or e[2] != w.data_ptr():
-            self._prepare_gemm(w, key[1], e[3])
-            e[1], e[2], e[4] = w._version, w.data_ptr(), 3
-            e[5].mark()
-        else:
-            e[5].wait()
-        return e[3]
-
-    @staticmethod
-    def _prepare_gemm(w, kind, buf):
-        w_is_kn, h2 = kind.startswith("kn"), kind.endswith("_h2")
-        k, n = (w.shape[0], w.shape[1]) if w_is_kn else (w.shape[1], w.shape[0])
-        _lib.call("t2h_gemm_f16x2_prepare" if h2 else "t2h_gemm_bx3_prepare", _lib.ptr(w), w.stride(0), k, n, 1 if w_is_kn else 0,
-                  _lib.ptr(buf), _lib.stream(), nbytes=(12 if h2 else 10) * w.numel())
+        return self._get(w, _MAT_KN if w_is_kn else _MAT_NK)
 
     def get_up(self, w: torch.Tensor, w_is_kn: bool) -> torch.Tensor:
         """The same for a ConvTranspose2d(2, stride 2) weight [Cin, Cout, 2, 2] whose memory is [Cin][2][2][Cout]: the matrix
         [Cin, (tap, co)] as the forward's [K, N] operand (``w_is_kn``) or as the data gradient's [N, K] operand."""
-        import weakref
-        key = (id(w), ("up_kn" if w_is_kn else "up_nk") + ("_h2" if _h2() else ""))
-        e = self.entries.get(key)
-        cin, n4 = w.shape[0], 4 * w.shape[1]
-        if e is None or e[0]() is not w:
-            k, n = (cin, n4) if w_is_kn else (n4, cin)
-            lib = _lib.load()
-            buf = torch.empty(int((lib.t2h_gemm_f16x2_weights_bytes if _h2() else lib.t2h_gemm_bx3_weights_bytes)(k, n)),
-                              dtype=torch.uint8, device=w.device)
-            e = self.entries[key] = [weakref.ref(w, lambda _r, kk=key: self.entries.pop(kk, None)), None, None, buf, 3, _lib.Ready()]
-        if e[1] != w._version or e[2] != w.data_ptr():
-            self._prepare_up(w, key[1], e[3])
-            e[1], e[2], e[4] = w._version, w.data_ptr(), 3
-            e[5].mark()
-        else:
-            e[5].wait()
-        return e[3]
+        return self._get(w, _UP_KN if w_is_kn else _UP_NK)
 
-    @staticmethod
-    def _prepare_up(w, kind, buf):
-        w_is_kn, h2 = kind.startswith("up_kn"), kind.endswith("_h2")
-        cin, n4 = w.shape[0], 4 * w.shape[1]
-        k, n = (cin, n4) if w_is_kn else (n4, cin)
-        _lib.call("t2h_gemm_f16x2_prepare" if h2 else "t2h_gemm_bx3_prepare", _lib.ptr(w), n4, k, n, 1 if w_is_kn else 0,
-                  _lib.ptr(buf), _lib.stream(), nbytes=(12 if h2 else 10) * w.numel())
+    def _get(self, w, kind):
+        h2 = CONV_PRECISION == "f16x2"
+        key = (id(w), kind, h2)
+        e = self.entries.get(key)
+        new = e is None or e.ref() is not w
+        if new or e.version != w._version or e.data_ptr != w.data_ptr():
+            dkind, a, b, ldw, _ = _split_desc(kind, w)
+            matrix = dkind >= 2
+            query, prepare, per_elem = _SPLIT_ENTRIES[matrix, h2]
+            if new:
+                buf = torch.empty(int(getattr(_lib.load(), query)(a, b)), dtype=torch.uint8, device=w.device)
+                e = self.entries[key] = _SplitEntry(weakref.ref(w, lambda _r, k=key: self.entries.pop(k, None)), buf)
+            if matrix:                                        # (w, ldw, K, N, w_is_kn), else (w, Cin, Cout, transposed)
+                _lib.call(prepare, _lib.ptr(w), ldw, a, b, 1 if dkind == 2 else 0, _lib.ptr(e.buf), _lib.stream(), nbytes=per_elem * w.numel())
+            else:
+                _lib.call(prepare, _lib.ptr(w), a, b, dkind, _lib.ptr(e.buf), _lib.stream(), nbytes=per_elem * w.numel())
+            e.version, e.data_ptr, e.maxslot = w._version, w.data_ptr(), 3
+            e.ready.mark()
+        else:
+            e.ready.wait()                                    # (filled on another stream: that fill first)
+        return e.buf
 
     def refresh(self, stale_only: bool = False):
         """Re-split every live weight (``stale_only``: those whose version counter or storage moved) into its existing buffer, all
@@ -254,27 +242,16 @@ class SplitWeightCache:
         ``Trainer.optimizer_boundary`` calls this right after the optimizer step, so the tiles that follow find every buffer
         current and launch nothing)."""
         todo = []
-        for (_, kind), e in list(self.entries.items()):
-            w = e[0]()
-            if w is None or not w.is_cuda or (stale_only and e[1] == w._version and e[2] == w.data_ptr()):
+        for (_, kind, h2), e in list(self.entries.items()):
+            w = e.ref()
+            if w is None or not w.is_cuda or (stale_only and e.version == w._version and e.data_ptr == w.data_ptr()):
                 continue
             d = _lib.PrepDesc()
-            d.w, d.wf = w.data_ptr(), e[3].data_ptr()
-            if isinstance(kind, str) and kind.startswith("up_"):           # [Cin, Cout, 2, 2] as the matrix [Cin][4 Cout]
-                kn, h2 = kind.startswith("up_kn"), kind.endswith("_h2")
-                cin, n4 = w.shape[0], 4 * w.shape[1]
-                d.kind, d.a, d.b, d.ldw = (2, cin, n4, n4) if kn else (3, n4, cin, n4)
-            elif isinstance(kind, str) and kind[:2] in ("kn", "nk"):
-                kn, h2 = kind.startswith("kn"), kind.endswith("_h2")
-                if w.dim() != 2 or w.stride(1) != 1:
-                    continue
-                d.kind, d.a, d.b, d.ldw = (2, w.shape[0], w.shape[1], w.stride(0)) if kn else (3, w.shape[1], w.shape[0], w.stride(0))
-            else:
-                h2 = kind in ("h2t", "h2f")
-                if not w.permute(0, 2, 3, 1).is_contiguous():
-                    continue
-                d.kind, d.a, d.b, d.ldw = (1 if kind in (True, "h2t") else 0), w.shape[1], w.shape[0], 0
-            d.h2, d.maxslot, d.trailer_word = int(h2), e[4], (e[3].numel() - 256) // 4 if h2 else 0
+            d.kind, d.a, d.b, d.ldw, batchable = _split_desc(kind, w)
+            if not batchable:
+                continue
+            d.w, d.wf = w.data_ptr(), e.buf.data_ptr()
+            d.h2, d.maxslot, d.trailer_word = int(h2), e.maxslot, (e.buf.numel() - 256) // 4 if h2 else 0
             todo.append((d, e, w))
         if not todo:
             return
@@ -283,8 +260,8 @@ class SplitWeightCache:
         done = _lib.Ready()
         done.mark()                                           # one event behind the batch, shared by its entries
         for d, e, w in todo:
-            e[1], e[2], e[4] = w._version, w.data_ptr(), (e[4] ^ 3) if d.h2 else e[4]
-            e[5] = done
+            e.version, e.data_ptr, e.maxslot = w._version, w.data_ptr(), (e.maxslot ^ 3) if d.h2 else e.maxslot
+            e.ready = done
 
 
 split_weights = SplitWeightCache()
@@ -295,20 +272,14 @@ def conv3x3_fwd_(x, w, bias, y, relu=False, accumulate=False):
     """y [B,Cout,H,W] (channels_last) = [y +] act(conv3x3(x, w) + bias); raw kernel call on NHWC-dense tensors."""
     b, cin, h, wd = x.shape
     cout = w.shape[0]
-    lib = _lib.load()
-    if bx3_applicable(b, h, wd, cin, cout):
-        flags = (_lib.RELU_OUT if relu else 0) | (_lib.ACCUM if accumulate else 0) | _bx3_flag()
-        nws = _lib.ws_bytes("t2h_conv3x3_bx3_fwd_workspace_bytes", b, h, wd, cin, cout)
-        ws = _lib.workspace(nws, x.device)
-        _lib.call("t2h_conv3x3_bx3_fwd", _lib.ptr(x), _lib.ptr(split_weights.get(w, False)),
-                  _lib.ptr(bias) if bias is not None else None, _lib.ptr(y), b, h, wd, cin, cout, flags, _lib.ptr(ws), nws, _lib.stream(),
-                  nbytes=4 * (x.numel() + y.numel() + w.numel()), flops=2 * 9 * cin * cout * b * h * wd,
-                  tag=_lib.timing() and f"t2h_conv3x3_fwd[{cin}->{cout},{h}x{wd}]")
-        return y
-    nws = _lib.ws_bytes("t2h_conv3x3_fwd_workspace_bytes", b, h, wd, cin, cout)
+    bx3 = bx3_applicable(b, h, wd, cin, cout)                # the split kernels on the prepared weights, else conv.hip on the raw ones
+    entry, query = (("t2h_conv3x3_bx3_fwd", "t2h_conv3x3_bx3_fwd_workspace_bytes") if bx3 else
+                    ("t2h_conv3x3_fwd", "t2h_conv3x3_fwd_workspace_bytes"))
+    flags = (_lib.RELU_OUT if relu else 0) | (_lib.ACCUM if accumulate else 0) | (_bx3_flag() if bx3 else 0)
+    nws = _lib.ws_bytes(query, b, h, wd, cin, cout)
     ws = _lib.workspace(nws, x.device)
-    flags = (_lib.RELU_OUT if relu else 0) | (_lib.ACCUM if accumulate else 0)
-    _lib.call("t2h_conv3x3_fwd", _lib.ptr(x), _lib.ptr(w), _lib.ptr(bias) if bias is not None else None, _lib.ptr(y),
+    wq = split_weights.get(w, False) if bx3 else w
+    _lib.call(entry, _lib.ptr(x), _lib.ptr(wq), _lib.ptr(bias) if bias is not None else None, _lib.ptr(y),
               b, h, wd, cin, cout, flags, _lib.ptr(ws), nws, _lib.stream(),
               nbytes=4 * (x.numel() + y.numel() + w.numel()), flops=2 * 9 * cin * cout * b * h * wd,
               tag=_lib.timing() and f"t2h_conv3x3_fwd[{cin}->{cout},{h}x{wd}]")
@@ -341,20 +312,15 @@ def conv3x3_dgrad_rank1_(gy, w, dx, mask, g, w1):
 def conv3x3_dgrad_(gy, w, dx, mask=None, accumulate=False):
     b, cout, h, wd = gy.shape
     cin = w.shape[1]
-    lib = _lib.load()
-    if bx3_applicable(b, h, wd, cin, cout):
-        nws = _lib.ws_bytes("t2h_conv3x3_bx3_dgrad_workspace_bytes", b, h, wd, cin, cout)
-        ws = _lib.workspace(nws, gy.device)
-        _lib.call("t2h_conv3x3_bx3_dgrad", _lib.ptr(gy), _lib.ptr(split_weights.get(w, True)), _lib.ptr(dx),
-                  _lib.ptr(mask) if mask is not None else None, b, h, wd, cin, cout, (_lib.ACCUM if accumulate else 0) | _bx3_flag(),
-                  _lib.ptr(ws), nws, _lib.stream(),
-                  nbytes=4 * (gy.numel() + dx.numel() * (2 if mask is not None else 1) + w.numel()),
-                  flops=2 * 9 * cin * cout * b * h * wd, tag=_lib.timing() and f"t2h_conv3x3_dgrad[{cout}->{cin},{h}x{wd}]")
-        return dx
-    nws = _lib.ws_bytes("t2h_conv3x3_dgrad_workspace_bytes", b, h, wd, cin, cout)
+    bx3 = bx3_applicable(b, h, wd, cin, cout)
+    entry, query = (("t2h_conv3x3_bx3_dgrad", "t2h_conv3x3_bx3_dgrad_workspace_bytes") if bx3 else
+                    ("t2h_conv3x3_dgrad", "t2h_conv3x3_dgrad_workspace_bytes"))
+    flags = (_lib.ACCUM if accumulate else 0) | (_bx3_flag() if bx3 else 0)
+    nws = _lib.ws_bytes(query, b, h, wd, cin, cout)
     ws = _lib.workspace(nws, gy.device)
-    _lib.call("t2h_conv3x3_dgrad", _lib.ptr(gy), _lib.ptr(w), _lib.ptr(dx), _lib.ptr(mask) if mask is not None else None,
-              b, h, wd, cin, cout, _lib.ACCUM if accumulate else 0, _lib.ptr(ws), nws, _lib.stream(),
+    wq = split_weights.get(w, True) if bx3 else w
+    _lib.call(entry, _lib.ptr(gy), _lib.ptr(wq), _lib.ptr(dx), _lib.ptr(mask) if mask is not None else None,
+              b, h, wd, cin, cout, flags, _lib.ptr(ws), nws, _lib.stream(),
               nbytes=4 * (gy.numel() + dx.numel() * (2 if mask is not None else 1) + w.numel()),
               flops=2 * 9 * cin * cout * b * h * wd, tag=_lib.timing() and f"t2h_conv3x3_dgrad[{cout}->{cin},{h}x{wd}]")
     return dx
@@ -365,24 +331,37 @@ def conv3x3_wgrad_(gy, x, dw, db, accumulate=False, defer=False):
     pass's batched one (``_lib.reduce_capture``)."""
     b, cout, h, wd = gy.shape
     cin = x.shape[1]
-    lib = _lib.load()
-    entry = "t2h_conv3x3_bx3_wgrad" if (BX3_WGRAD and bx3_applicable(b, h, wd, cin, cout)) else "t2h_conv3x3_wgrad"
-    if entry == "t2h_conv3x3_bx3_wgrad":
-        nws = _lib.ws_bytes("t2h_conv3x3_bx3_wgrad_workspace_bytes", b, h, wd, cin, cout)
-        ws = _lib.workspace(nws, gy.device)
-        _lib.call(entry, _lib.ptr(gy), _lib.ptr(x), _lib.ptr(dw), _lib.ptr(db) if db is not None else None,
-                  b, h, wd, cin, cout, (_lib.ACCUM if accumulate else 0) | _bx3_flag() | (_lib.defer_reduce(ws, dw) if defer else 0),
-                  _lib.ptr(ws), nws, _lib.stream(),
-                  nbytes=4 * (gy.numel() + x.numel() + dw.numel()), flops=2 * 9 * cin * cout * b * h * wd,
-                  tag=_lib.timing() and f"t2h_conv3x3_wgrad[{cin}->{cout},{h}x{wd}]")
-        return
-    nws = _lib.ws_bytes("t2h_conv3x3_wgrad_workspace_bytes", b, h, wd, cin, cout)
+    bx3 = BX3_WGRAD and bx3_applicable(b, h, wd, cin, cout)
+    entry, query = (("t2h_conv3x3_bx3_wgrad", "t2h_conv3x3_bx3_wgrad_workspace_bytes") if bx3 else
+                    ("t2h_conv3x3_wgrad", "t2h_conv3x3_wgrad_workspace_bytes"))
+    nws = _lib.ws_bytes(query, b, h, wd, cin, cout)
     ws = _lib.workspace(nws, gy.device)
-    _lib.call("t2h_conv3x3_wgrad", _lib.ptr(gy), _lib.ptr(x), _lib.ptr(dw), _lib.ptr(db) if db is not None else None,
-              b, h, wd, cin, cout, (_lib.ACCUM if accumulate else 0) | (_lib.defer_reduce(ws, dw) if defer else 0), _lib.ptr(ws), nws,
-              _lib.stream(),
+    flags = (_lib.ACCUM if accumulate else 0) | (_bx3_flag() if bx3 else 0) | (_lib.defer_reduce(ws, dw) if defer else 0)
+    _lib.call(entry, _lib.ptr(gy), _lib.ptr(x), _lib.ptr(dw), _lib.ptr(db) if db is not None else None,
+              b, h, wd, cin, cout, flags, _lib.ptr(ws), nws, _lib.stream(),
               nbytes=4 * (gy.numel() + x.numel() + dw.numel()), flops=2 * 9 * cin * cout * b * h * wd,
               tag=_lib.timing() and f"t2h_conv3x3_wgrad[{cin}->{cout},{h}x{wd}]")
+
+
+def _relu_masked(g, y):
+    """g * (y > 0), out of place: the ReLU backward of a conv whose consumer did not fold the mask into its data gradient."""
+    gm = torch.empty_like(g, memory_format=torch.channels_last)
+    _lib.call("t2h_relu_mask", _lib.ptr(g), _lib.ptr(y), _lib.ptr(gm), g.numel(), _lib.stream(), nbytes=12 * g.numel())
+    return gm
+
+
+def _param_grad_targets(weight, bias):
+    """(dw, db, direct) -- where a layer's weight / bias gradient goes: accumulated straight into the existing ``.grad`` buffers
+    (the trainer's bucket) under ``mlp.direct_grad_accumulation`` when their layout allows it (``direct``: the autograd function
+    then returns None for them), else fresh tensors to be written."""
+    wg = weight.grad
+    if mlp._DIRECT_ACCUM and wg is not None and wg.permute(0, 2, 3, 1).is_contiguous():
+        if bias is None:
+            return wg, None, True
+        bg = bias.grad
+        if bg is not None and bg.is_contiguous():
+            return wg, bg, True
+    return (torch.empty_like(weight, memory_format=torch.channels_last), torch.empty_like(bias) if bias is not None else None, False)
 
 
 class _Conv3x3(torch.autograd.Function):
@@ -408,12 +387,7 @@ class _Conv3x3(torch.autograd.Function):
         relu, mask_input, grad_premasked = ctx.conf
         g = _as_cl(g)
         w = _w_cl(weight)
-        if relu and not grad_premasked:
-            gm = torch.empty_like(g, memory_format=torch.channels_last)
-            _lib.call("t2h_relu_mask", _lib.ptr(g), _lib.ptr(y), _lib.ptr(gm), g.numel(), _lib.stream(),
-                      nbytes=12 * g.numel())
-        else:
-            gm = g
+        gm = _relu_masked(g, y) if (relu and not grad_premasked) else g
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x, memory_format=torch.channels_last)
@@ -429,22 +403,19 @@ OVERLAP_MAX_PIXELS = int(os.environ.get("T2H_OVERLAP_CONV_MAX_PIXELS", str(512 *
 def _conv3x3_param_grads(gm, x, weight, bias):
     """Weight / bias gradient of one conv3x3: straight into the existing ``.grad`` buffers (the trainer's bucket) under
     ``mlp.direct_grad_accumulation`` -- returns (None, None) then -- else as fresh tensors."""
-    wg, bg = weight.grad, (bias.grad if bias is not None else None)
-    if (mlp._DIRECT_ACCUM and wg is not None and wg.permute(0, 2, 3, 1).is_contiguous()
-            and (bias is None or (bg is not None and bg.is_contiguous()))):
+    dw, db, direct = _param_grad_targets(weight, bias)
+    if direct:
         side = mlp._CONV_WGRAD_STREAM
         if side is not None and x.shape[2] * x.shape[3] <= OVERLAP_MAX_PIXELS:
             # small planes: the weight gradient (off the backward's critical path: nothing reads the bucket before the
             # optimizer step) runs on a side stream beside the next layers' data gradients -- these launches are
             # latency-bound and leave most CUs idle; the trainer joins the stream at the end of the tile
             with mlp.fork_to(side):
-                conv3x3_wgrad_(gm, x, wg, bg, accumulate=True, defer=True)
+                conv3x3_wgrad_(gm, x, dw, db, accumulate=True, defer=True)
             mlp.hold(gm, x)
         else:
-            conv3x3_wgrad_(gm, x, wg, bg, accumulate=True, defer=True)
+            conv3x3_wgrad_(gm, x, dw, db, accumulate=True, defer=True)
         return None, None
-    dw = torch.empty_like(weight, memory_format=torch.channels_last)
-    db = torch.empty_like(bias) if bias is not None else None
     conv3x3_wgrad_(gm, x, dw, db)
     return dw, db
 
@@ -482,22 +453,14 @@ class _Conv3x3Small(torch.autograd.Function):
         w = _w_cl(weight)
         b, cin, h, wd = x.shape
         cout = w.shape[0]
-        if relu and not grad_premasked:
-            gm = torch.empty_like(g, memory_format=torch.channels_last)
-            _lib.call("t2h_relu_mask", _lib.ptr(g), _lib.ptr(y), _lib.ptr(gm), g.numel(), _lib.stream(), nbytes=12 * g.numel())
-        else:
-            gm = g
+        gm = _relu_masked(g, y) if (relu and not grad_premasked) else g
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x, memory_format=torch.channels_last)
             _lib.call("t2h_conv3x3_smallcin_dgrad", _lib.ptr(gm), _lib.ptr(w), _lib.ptr(dx), b, h, wd, cin, cout, 0,
                       _lib.stream(), nbytes=4 * (gm.numel() + dx.numel()), flops=2 * 9 * cin * cout * b * h * wd,
                       tag=_lib.timing() and f"t2h_conv3x3_smallcin_dgrad[{cout}->{cin},{h}x{wd}]")
-        wg, bg = weight.grad, bias.grad
-        direct = (mlp._DIRECT_ACCUM and wg is not None and wg.permute(0, 2, 3, 1).is_contiguous() and bg is not None
-                  and bg.is_contiguous())
-        dw = wg if direct else torch.empty_like(weight, memory_format=torch.channels_last)
-        db = bg if direct else torch.empty_like(bias)
+        dw, db, direct = _param_grad_targets(weight, bias)
         nws = _lib.ws_bytes("t2h_conv3x3_smallcin_wgrad_workspace_bytes", cin, cout)
         ws = _lib.workspace(nws, g.device)
         _lib.call("t2h_conv3x3_smallcin_wgrad", _lib.ptr(gm), _lib.ptr(x), _lib.ptr(dw), _lib.ptr(db), b, h, wd, cin, cout,
@@ -577,12 +540,7 @@ class _Conv1x1(torch.autograd.Function):
             _lib.call("t2h_linear_dgrad", _lib.ptr(g), ldg, _lib.ptr(w2), _lib.ptr(dx), cin, m, cin, cout, None, 0, 0,
                       _lib.stream(), nbytes=4 * (m * cin + m * cout + cin * cout), flops=2 * m * cin * cout,
                       tag=_lib.timing() and f"t2h_linear_dgrad[N={cout},K={cin}]")
-        wg, bg = weight.grad, (bias.grad if bias is not None else None)
-        direct = (mlp._DIRECT_ACCUM and wg is not None and wg.permute(0, 2, 3, 1).is_contiguous()
-                  and (bias is None or (bg is not None and bg.is_contiguous())))
-        dw = wg if direct else torch.empty_like(weight, memory_format=torch.channels_last)
-        db = bg if direct else (torch.empty_like(bias) if bias is not None else None)
-        lib = _lib.load()
+        dw, db, direct = _param_grad_targets(weight, bias)
         nws = _lib.ws_bytes("t2h_linear_wgrad_workspace_bytes", m, cin, cout)
         ws = _lib.workspace(nws, g.device)
         _lib.call("t2h_linear_wgrad", _lib.ptr(g), ldg, _lib.ptr(x), cin, m, cin, cout, _lib.ACCUM if direct else 0,
@@ -624,83 +582,88 @@ def _up_bx3(x, weight, w) -> bool:
                 and _lib.ws_bytes("t2h_upconv2x2_bx3_supported", b, h, wd, cin, weight.shape[1]))
 
 
+def upconv2x2_fwd_(x, w, bias, addend, y, bx3: bool):
+    """y [B,Cout,2H,2W] = [addend +] upconv2x2(x, w) + bias; raw kernel call on NHWC-dense tensors, ``w`` [Cin][2][2][Cout] in
+    memory.  ``bx3``: on the split kernels with the prepared weights (``_up_bx3``), else conv.hip."""
+    b, cin, h, wd = x.shape
+    cout = w.shape[1]
+    entry, name = ("t2h_upconv2x2_bx3_fwd", "t2h_upconv2x2_bx3_fwd") if bx3 else ("t2h_upconv2x2_fwd_add", "t2h_upconv2x2_fwd")
+    _lib.call(entry, _lib.ptr(x), _lib.ptr(split_weights.get_up(w, True) if bx3 else w), _lib.ptr(bias) if bias is not None else None,
+              _lib.ptr(addend) if addend is not None else None, _lib.ptr(y), b, h, wd, cin, cout,
+              _lib.F16X2 if (bx3 and _h2()) else 0, _lib.stream(),
+              nbytes=4 * (x.numel() + y.numel() * (2 if addend is not None else 1)) + (6 if bx3 else 4) * w.numel(),
+              flops=2 * 4 * cin * cout * b * h * wd, tag=_lib.timing() and f"{name}[{cin}->{cout},{h}x{wd}]")
+    return y
+
+
+def upconv2x2_dgrad_(g, ldg: int, w, dx, bx3: bool):
+    """dx = the data gradient of upconv2x2.  The split kernel reads ``g`` with a pixel stride of ``ldg`` floats (a channel slice
+    in place); conv.hip wants it dense."""
+    b, cin, h, wd = dx.shape
+    cout = w.shape[1]
+    entry, query = (("t2h_upconv2x2_bx3_dgrad", "t2h_upconv2x2_bx3_dgrad_workspace_bytes") if bx3 else
+                    ("t2h_upconv2x2_dgrad", "t2h_upconv2x2_dgrad_workspace_bytes"))
+    nws = _lib.ws_bytes(query, b, h, wd, cin, cout)
+    ws = _lib.workspace(nws, g.device)
+    operands = (_lib.ptr(g), ldg, _lib.ptr(split_weights.get_up(w, False))) if bx3 else (_lib.ptr(g), _lib.ptr(w))
+    _lib.call(entry, *operands, _lib.ptr(dx), b, h, wd, cin, cout, _lib.F16X2 if (bx3 and _h2()) else 0, _lib.ptr(ws), nws,
+              _lib.stream(), nbytes=4 * (g.numel() + dx.numel()) + (6 if bx3 else 4) * w.numel(),
+              flops=2 * 4 * cin * cout * b * h * wd, tag=_lib.timing() and f"{entry}[{cout}->{cin},{h}x{wd}]")
+    return dx
+
+
+def upconv2x2_wgrad_(g, ldg: int, x, dw, db, bx3: bool, accumulate=False, defer=False):
+    """Weight AND bias gradient from one kernel (the bias gradient is the column sum of the dY tiles it stages anyway); ``g`` /
+    ``ldg`` as in ``upconv2x2_dgrad_``, ``defer`` as in ``conv3x3_wgrad_``."""
+    b, cin, h, wd = x.shape
+    cout = dw.shape[1]
+    entry, query = (("t2h_upconv2x2_bx3_wgrad", "t2h_upconv2x2_bx3_wgrad_workspace_bytes") if bx3 else
+                    ("t2h_upconv2x2_wgrad_bias", "t2h_upconv2x2_wgrad_workspace_bytes"))
+    nws = _lib.ws_bytes(query, b, h, wd, cin, cout)
+    ws = _lib.workspace(nws, g.device)
+    flags = (_lib.ACCUM if accumulate else 0) | (_lib.defer_reduce(ws, dw) if defer else 0) | (_lib.F16X2 if (bx3 and _h2()) else 0)
+    operands = (_lib.ptr(g), ldg) if bx3 else (_lib.ptr(g),)
+    _lib.call(entry, *operands, _lib.ptr(x), _lib.ptr(dw), None if db is None else _lib.ptr(db), b, h, wd, cin, cout, flags,
+              _lib.ptr(ws), nws, _lib.stream(), nbytes=4 * (g.numel() + x.numel() + dw.numel()),
+              flops=2 * 4 * cin * cout * b * h * wd, tag=_lib.timing() and f"{entry}[{cin}->{cout},{h}x{wd}]")
+
+
 class _UpConv2x2(torch.autograd.Function):
-    """nn.ConvTranspose2d(kernel_size=2, stride=2) (upconv2x2, alto.py:175,215-218,236) on csrc/conv.hip."""
+    """nn.ConvTranspose2d(kernel_size=2, stride=2) (upconv2x2, alto.py:175,215-218,236) on csrc/conv.hip / csrc/conv_bx3.hip."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, addend):
         x = _as_cl(x)
         w = _w_cl(weight)                                   # [Cin][2][2][Cout] in memory
         b, cin, h, wd = x.shape
-        cout = weight.shape[1]
-        y = _empty_cl(b, cout, 2 * h, 2 * wd, x.device)
+        y = _empty_cl(b, weight.shape[1], 2 * h, 2 * wd, x.device)
         if addend is not None:
             addend = _as_cl(addend)
             if addend.shape != y.shape:
                 raise ValueError("upconv2x2: addend must have the output's shape")
         ctx.has_addend = addend is not None
         ctx.bx3 = _up_bx3(x, weight, w)
-        if ctx.bx3:
-            _lib.call("t2h_upconv2x2_bx3_fwd", _lib.ptr(x), _lib.ptr(split_weights.get_up(w, True)),
-                      _lib.ptr(bias) if bias is not None else None, _lib.ptr(addend) if addend is not None else None, _lib.ptr(y),
-                      b, h, wd, cin, cout, _lib.F16X2 if _h2() else 0, _lib.stream(),
-                      nbytes=4 * (x.numel() + y.numel() * (2 if addend is not None else 1)) + 6 * w.numel(),
-                      flops=2 * 4 * cin * cout * b * h * wd, tag=_lib.timing() and f"t2h_upconv2x2_bx3_fwd[{cin}->{cout},{h}x{wd}]")
-            ctx.save_for_backward(x, weight, bias)
-            return y
-        _lib.call("t2h_upconv2x2_fwd_add", _lib.ptr(x), _lib.ptr(w), _lib.ptr(bias) if bias is not None else None,
-                  _lib.ptr(addend) if addend is not None else None, _lib.ptr(y),
-                  b, h, wd, cin, cout, 0, _lib.stream(),
-                  nbytes=4 * (x.numel() + y.numel() * (2 if addend is not None else 1) + w.numel()),
-                  flops=2 * 4 * cin * cout * b * h * wd, tag=_lib.timing() and f"t2h_upconv2x2_fwd[{cin}->{cout},{h}x{wd}]")
+        upconv2x2_fwd_(x, w, bias, addend, y, ctx.bx3)
         ctx.save_for_backward(x, weight, bias)
         return y
 
     @staticmethod
     def backward(ctx, g):
         x, weight, bias = ctx.saved_tensors
-        b, cin, h, wd = x.shape
-        cout = weight.shape[1]
-        up = "t2h_upconv2x2_bx3_wgrad" if (ctx.bx3 and BX3_WGRAD and wd >= 32) else "t2h_upconv2x2_wgrad_bias"
+        wgrad_bx3 = ctx.bx3 and BX3_WGRAD and x.shape[3] >= 32     # (the data gradient: ctx.bx3)
         g0 = g
         # the split kernels read a channel slice of a concatenation's gradient in place (pixel stride ldg); the fp32 ones want it dense
-        g, ldg = _cl_ld(g) if (ctx.bx3 and up == "t2h_upconv2x2_bx3_wgrad") else (_as_cl(g), cout)
+        g, ldg = _cl_ld(g) if wgrad_bx3 else (_as_cl(g), weight.shape[1])
         w = _w_cl(weight)
-        lib = _lib.load()
-        flops = 2 * 4 * cin * cout * b * h * wd
         dx = None
         if ctx.needs_input_grad[0]:
-            dx = torch.empty_like(x, memory_format=torch.channels_last)
-        if dx is not None and ctx.bx3:
-            nws = _lib.ws_bytes("t2h_upconv2x2_bx3_dgrad_workspace_bytes", b, h, wd, cin, cout)
-            ws = _lib.workspace(nws, g.device)
-            _lib.call("t2h_upconv2x2_bx3_dgrad", _lib.ptr(g), ldg, _lib.ptr(split_weights.get_up(w, False)), _lib.ptr(dx),
-                      b, h, wd, cin, cout, _lib.F16X2 if _h2() else 0, _lib.ptr(ws), nws, _lib.stream(),
-                      nbytes=4 * (g.numel() + dx.numel()) + 6 * w.numel(), flops=flops,
-                      tag=_lib.timing() and f"t2h_upconv2x2_bx3_dgrad[{cout}->{cin},{h}x{wd}]")
-        elif dx is not None:
-            nws = _lib.ws_bytes("t2h_upconv2x2_dgrad_workspace_bytes", b, h, wd, cin, cout)
-            ws = _lib.workspace(nws, g.device)
-            _lib.call("t2h_upconv2x2_dgrad", _lib.ptr(g), _lib.ptr(w), _lib.ptr(dx), b, h, wd, cin, cout, 0, _lib.ptr(ws), nws,
-                      _lib.stream(), nbytes=4 * (g.numel() + dx.numel() + w.numel()), flops=flops,
-                      tag=_lib.timing() and f"t2h_upconv2x2_dgrad[{cout}->{cin},{h}x{wd}]")
-        wg, bg = weight.grad, (bias.grad if bias is not None else None)
-        direct = (mlp._DIRECT_ACCUM and wg is not None and wg.permute(0, 2, 3, 1).is_contiguous()
-                  and (bias is None or (bg is not None and bg.is_contiguous())))
-        dw = wg if direct else torch.empty_like(weight, memory_format=torch.channels_last)
-        db = bg if direct else (torch.empty_like(bias) if bias is not None else None)
-        nws = _lib.ws_bytes(up.replace("_bias", "") + "_workspace_bytes", b, h, wd, cin, cout)
-        # weight AND bias gradient from one kernel (the bias gradient is the column sum of the dY tiles it stages anyway); like the
-        # 3x3 weight gradients on the trainer's side stream when there is one (_conv3x3_param_grads) -- unless g is also handed on
-        # as the addend's gradient: its consumer may accumulate into it in place on the main stream (mlp.sole_owner)
+            dx = upconv2x2_dgrad_(g, ldg, w, torch.empty_like(x, memory_format=torch.channels_last), ctx.bx3)
+        dw, db, direct = _param_grad_targets(weight, bias)
+        # like the 3x3 weight gradients on the trainer's side stream when there is one (_conv3x3_param_grads) -- unless g is also
+        # handed on as the addend's gradient: its consumer may accumulate into it in place on the main stream (mlp.sole_owner)
         side = mlp._CONV_WGRAD_STREAM if (direct and not ctx.has_addend) else None
         with mlp.fork_to(side) if side is not None else contextlib.nullcontext():
-            ws = _lib.workspace(nws, g.device)
-            _lib.call(up, _lib.ptr(g), *((ldg,) if up == "t2h_upconv2x2_bx3_wgrad" else ()), _lib.ptr(x), _lib.ptr(dw),
-                      None if db is None else _lib.ptr(db), b, h, wd, cin, cout,
-                      ((_lib.ACCUM | _lib.defer_reduce(ws, dw)) if direct else 0) | (_lib.F16X2 if (_h2() and up.endswith("bx3_wgrad")) else 0),
-                      _lib.ptr(ws), nws, _lib.stream(), nbytes=4 * (g.numel() + x.numel() + dw.numel()), flops=flops,
-                      tag=_lib.timing() and f"{up}[{cin}->{cout},{h}x{wd}]")
+            upconv2x2_wgrad_(g, ldg, x, dw, db, wgrad_bx3, accumulate=direct, defer=direct)
         if side is not None:
             mlp.hold(g, x)
         ga = g0 if ctx.has_addend else None
@@ -925,13 +888,7 @@ def _maxpool_ok(x: torch.Tensor, pool) -> bool:
 
 def maxpool2x2(x: torch.Tensor, pool: torch.nn.MaxPool2d = None) -> torch.Tensor:
     """``nn.MaxPool2d(kernel_size=2, stride=2)(x)`` on channels_last planes (same winners on ties as ATen)."""
-    ok = (USE_HIP_CONV and x.dim() == 4 and x.is_cuda and x.dtype == torch.float32 and x.shape[1] % 4 == 0
-          and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0 and x.shape[2] >= 2 and x.shape[3] >= 2)
-    if pool is not None:
-        k, st = pool.kernel_size, pool.stride
-        ok = ok and (k in (2, (2, 2))) and (st in (2, (2, 2))) and pool.padding in (0, (0, 0)) and not pool.ceil_mode \
-            and pool.dilation in (1, (1, 1)) and not pool.return_indices
-    if not ok:
+    if not _maxpool_ok(x, pool):
         _lib.library_fallback(f"max_pool2d on {tuple(x.shape)} (ATen)")
         return pool(x) if pool is not None else F.max_pool2d(x, 2, 2)
     return _MaxPool2x2.apply(x)
