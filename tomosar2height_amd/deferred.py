@@ -139,8 +139,15 @@ class _ComposeStack(torch.autograd.Function):
 
 def _transpose(src, dst):
     """dst [n, m] = src [m, n]^T, both contiguous row-major (the [B, C, P] -> [B, P, C] layout kernel with B = 1)."""
-    m, n = src.shape
-    _lib.call("t2h_nchw_to_nhwc", _lib.ptr(src), 1, m, n, _lib.ptr(dst), _lib.stream(), nbytes=8 * m * n)
+    ops.nchw_to_nhwc_(src, 1, src.shape[0], src.shape[1], dst)
+
+
+def _compose_step(a_prev, const_prev, params):
+    """One level of the compose chain: (a_all, const) of the level with weights ``params`` = (wc, bc, w1, b1) from the previous
+    level's pair (None, None before the first): const_k = const_{k-1} Wc_k^T + bc_k + b1_k, const_{-1} = 0."""
+    wc, bc, w1, b1 = params
+    a_all = _ComposeStack.apply(a_prev, wc, w1)
+    return a_all, ((bc + b1).reshape(1, -1) if const_prev is None else mlp.linear(const_prev, wc, bc) + b1.reshape(1, -1))
 
 
 class _DeferredLevel(torch.autograd.Function):
@@ -163,19 +170,20 @@ class _DeferredLevel(torch.autograd.Function):
                    _lib.ws_bytes("t2h_sample_bwd_workspace_bytes", tile.B, tile.N, tile.nbits, tile.level(r), c2) > 0)
         # (the on-chip pass needs 2 x 2 blocks of sampling cells: not the 1 x 1 plane of level == nbits)
         on_chip = (bits_ok if need_bwd else (c2 % 256 == 0 and tile.n_points > 0)) and ON_CHIP_HIDDEN and tile.level(r) < tile.nbits
-        if on_chip and tile.n_points >= ON_CHIP_MIN_PTS_PER_CELL * tile.B * r * r:
+        on_chip = on_chip and tile.n_points >= ON_CHIP_MIN_PTS_PER_CELL * tile.B * r * r
+        # the backward needs only the sign pattern of h: where its fused form will run, keep 1 bit per element (written by the
+        # kernel's ballots) -- 1/32 of the bytes to keep and to re-read.  The on-chip pass has nothing else to leave behind.
+        want_bits = need_bwd and (on_chip or bits_ok)
+        bits = torch.empty(tile.n_points * (c2 // 256) * 4, dtype=torch.int64, device=q_rows.device) if want_bits else None
+        if on_chip:
             # coarse sampling level: interpolation, ReLU, sign bits and the per-cell sums of the finest needed resolution in one
             # pass over the cells -- the hidden activations are never written to memory (t2h_sample_relu_cellsums)
-            bits = None
-            if need_bwd:
-                bits = torch.empty(tile.n_points * (c2 // 256) * 4, dtype=torch.int64, device=q_rows.device)
-            lo, hi = state.off[idx + 1], state.off[idx + 2]
             levels = state.needed(idx + 1)
-            finest = state._matrix(state.S, levels[0])[:, lo:hi]
+            finest = state.sums(idx + 1, levels[0])
             # the next coarser needed resolution comes out of the same pass (the four children of a cell are in registers)
             second = None
             if len(levels) > 1 and levels[1] == levels[0] + 1 and levels[0] < tile.level(r):
-                second = state._matrix(state.S, levels[1])[:, lo:hi]
+                second = state.sums(idx + 1, levels[1])
             order = tile.cell_order(tile.level(r))
             _lib.call("t2h_sample_relu_cellsums_ordered", _lib.ptr(q_rows), _lib.ptr(tile.pts), tile.dim, _lib.ptr(tile.off0), tile.B,
                       tile.N, tile.nbits, tile.level(r), levels[0], c2, finest.data_ptr(), finest.stride(0),
@@ -186,16 +194,8 @@ class _DeferredLevel(torch.autograd.Function):
                       tag=_lib.timing() and f"t2h_sample_relu_cellsums[C={c2},r={r}]")
             state.pool_down(idx + 1, start=1 if second is not None else 0)
             return _DeferredLevel._finish(ctx, state, idx, r, a_all, const, bits, True)
-        h = torch.empty(tile.n_points, c2, dtype=torch.float32, device=q_rows.device)
-        # the backward needs only the sign pattern of h: where its fused form will run, keep 1 bit per element (written by the
-        # sample kernel's ballots) and let h go after the per-cell sums -- 1/32 of the bytes to keep and to re-read
-        bits = None
-        if bits_ok and need_bwd:
-            bits = torch.empty(tile.n_points * (c2 // 256) * 4, dtype=torch.int64, device=q_rows.device)
-        _lib.call("t2h_sample_fwd_relu", _lib.ptr(q_rows), _lib.ptr(tile.pts), tile.dim, tile.B, tile.N, r, c2, _lib.ptr(h),
-                  None if bits is None else _lib.ptr(bits), _lib.stream(),
-                  nbytes=4 * c2 * tile.n_points + 8 * tile.n_points + 4 * q_rows.numel() + (c2 // 8) * tile.n_points * (bits is not None),
-                  tag=_lib.timing() and f"t2h_sample_fwd_relu[C={c2},r={r}]")
+        h = torch.empty(tile.n_points, c2, dtype=torch.float32, device=q_rows.device)      # (let go after the per-cell sums if bits)
+        ops.sample_fwd_relu_(tile, q_rows, r, h, bits)
         state.write_sums(idx + 1, h)
         return _DeferredLevel._finish(ctx, state, idx, r, a_all, const, h if bits is None else bits, bits is not None)
 
@@ -234,7 +234,7 @@ class _DeferredLevel(torch.autograd.Function):
         cnt = counts(tile, lv)
         # through the mean / bias epilogue
         dacc = torch.empty_like(g)
-        cached = state.cache is not None and not ctx.needs_input_grad[1]
+        cached = state.cache is not None and not ctx.needs_input_grad[1]      # maps from the trainer's ComposeCache
         dconst = torch.empty(ctx.const_shape, dtype=torch.float32, device=g.device) if (ctx.needs_input_grad[2] or cached) else None
         ws_bytes = _lib.ws_bytes("t2h_mean_bias_bwd_workspace_bytes", p, c)
         ws = _lib.workspace(ws_bytes, g.device)
@@ -242,12 +242,12 @@ class _DeferredLevel(torch.autograd.Function):
                   _lib.ptr(ws), ws_bytes, _lib.stream(), nbytes=8 * p * c + 4 * p)
         x = state.S[lv][:, :k]
         da = ga_thru
-        if state.cache is not None and not ctx.needs_input_grad[1]:
-            # maps from the trainer's ComposeCache: this tile's share goes onto the persistent sums (zeroed by flush())
+        if cached:
+            # this tile's share goes onto the persistent sums (zeroed by flush())
             e = state.cache.levels[idx]
-            e["ready"].wait()
-            mlp.linear_wgrad_(x, dacc, e["ga"], None, accumulate=True, defer=True)   # += x^T dacc (read at flush(): after the pass)
-            e["gconst"].add_(dconst)
+            e.ready.wait()
+            mlp.linear_wgrad_(x, dacc, e.ga, None, accumulate=True, defer=True)      # += x^T dacc (read at flush(): after the pass)
+            e.gconst.add_(dconst)
             dconst = None
             state.cache.pending = True
         elif ctx.needs_input_grad[1]:
@@ -278,6 +278,15 @@ class _DeferredLevel(torch.autograd.Function):
         return dq, da, dconst, dbase, None, None, None
 
 
+class _CachedLevel:
+    """One level of a ``ComposeCache``: the maps for ``params`` at ``versions``, their accumulated gradients, who may read them."""
+    __slots__ = ("params", "versions", "a_all", "const", "ga", "gconst", "ready")
+
+    def __init__(self, params, versions, a_all, const):
+        self.params, self.versions, self.a_all, self.const = params, versions, a_all, const
+        self.ga, self.gconst, self.ready = torch.zeros_like(a_all), torch.zeros_like(const), _lib.Ready()
+
+
 class ComposeCache:
     """The composed maps ``a_all`` / ``const`` of the deferred levels depend on the WEIGHTS only, and their backward is linear in
     the gradient they receive -- so between two optimizer steps (the reference accumulates 64 tiles per step, trainer.py:72-89)
@@ -291,91 +300,78 @@ class ComposeCache:
     captured hipGraph keeps reading current values."""
 
     def __init__(self):
-        self.levels = []            # per deferred level: dict(params, versions, a_all, const, ga, gconst)
+        self.levels = []            # one _CachedLevel per deferred level
         self.pending = False
 
-    @staticmethod
-    def _versions(params):
-        return tuple(p._version for p in params)
-
     def _compute(self, idx, params):
-        wc, bc, w1, b1 = params
         prev = self.levels[idx - 1] if idx > 0 else None
         with torch.no_grad():
-            a_all = _ComposeStack.apply(None if prev is None else prev["a_all"], wc, w1)
-            if prev is None:
-                const = (bc + b1).reshape(1, -1)
-            else:
-                const = mlp.linear(prev["const"], wc, bc) + b1.reshape(1, -1)
-        return a_all, const
+            return _compose_step(None if prev is None else prev.a_all, None if prev is None else prev.const, params)
 
     def get(self, idx, params):
         """(a_all, const) of deferred level ``idx`` for the current weights (levels are asked for in order within a forward)."""
         params = tuple(params)
         if idx > len(self.levels):
             raise RuntimeError("ComposeCache: levels must be requested in order")
-        ver = self._versions(params)
+        ver = tuple(p._version for p in params)
         if idx == len(self.levels):
-            a_all, const = self._compute(idx, params)
-            self.levels.append({"params": params, "versions": ver, "a_all": a_all, "const": const,
-                                "ga": torch.zeros_like(a_all), "gconst": torch.zeros_like(const), "ready": _lib.Ready()})
-            self.levels[idx]["ready"].mark()
-        else:
-            e = self.levels[idx]
-            if any(p is not q for p, q in zip(e["params"], params)):
-                raise RuntimeError("ComposeCache: a different network uses this cache")
-            if e["versions"] != ver:
-                if self.pending:
-                    raise RuntimeError("ComposeCache: weights changed with unflushed gradients (call flush() before the optimizer step)")
-                a_all, const = self._compute(idx, params)
-                e["a_all"].copy_(a_all)
-                e["const"].copy_(const)
-                e["versions"] = ver
-                e["ready"].mark()
-            else:
-                e["ready"].wait()                             # (computed on another stream, e.g. the other tile stream: that first)
+            self.levels.append(_CachedLevel(params, ver, *self._compute(idx, params)))
+            self.levels[idx].ready.mark()
+            return self.levels[idx].a_all, self.levels[idx].const
         e = self.levels[idx]
-        return e["a_all"], e["const"]
+        if any(p is not q for p, q in zip(e.params, params)):
+            raise RuntimeError("ComposeCache: a different network uses this cache")
+        if e.versions != ver:
+            if self.pending:
+                raise RuntimeError("ComposeCache: weights changed with unflushed gradients (call flush() before the optimizer step)")
+            a_all, const = self._compute(idx, params)
+            e.a_all.copy_(a_all)
+            e.const.copy_(const)
+            e.versions = ver
+            e.ready.mark()
+        else:
+            e.ready.wait()                                    # (computed on another stream, e.g. the other tile stream: that first)
+        return e.a_all, e.const
 
     def snapshot(self):
         """The accumulated gradients (for a caller that runs passes whose gradients must not count: hipGraph warm-up / capture)."""
-        return [(e["ga"].clone(), e["gconst"].clone()) for e in self.levels], self.pending
+        return [(e.ga.clone(), e.gconst.clone()) for e in self.levels], self.pending
 
     def restore(self, snap):
         saved, self.pending = snap
         for i, e in enumerate(self.levels):          # levels created after the snapshot start from zero
             if i < len(saved):
-                e["ga"].copy_(saved[i][0])
-                e["gconst"].copy_(saved[i][1])
+                e.ga.copy_(saved[i][0])
+                e.gconst.copy_(saved[i][1])
             else:
-                e["ga"].zero_()
-                e["gconst"].zero_()
+                e.ga.zero_()
+                e.gconst.zero_()
 
     def refresh(self):
         """Recompute every level's maps in place (after an optimizer step; needed explicitly only under hipGraph replay, where
         no Python runs per tile)."""
         for idx, e in enumerate(self.levels):
-            e["versions"] = None
-            self.get(idx, e["params"])
+            e.versions = None
+            self.get(idx, e.params)
+
+    def drop_accumulated(self):
+        """Forget the gradients accumulated since the last flush."""
+        for e in self.levels:
+            e.ga.zero_()
+            e.gconst.zero_()
+        self.pending = False
 
     def flush(self):
         """The compose chain's backward, once, on the gradients accumulated since the last flush."""
         if not self.levels:
             return
-        outs, grads, a_prev, const = [], [], None, None
+        outs, a_all, const = [], None, None
         with torch.enable_grad():
             for e in self.levels:
-                wc, bc, w1, b1 = e["params"]
-                a_all = _ComposeStack.apply(a_prev, wc, w1)
-                const = (bc + b1).reshape(1, -1) if const is None else mlp.linear(const, wc, bc) + b1.reshape(1, -1)
+                a_all, const = _compose_step(a_all, const, e.params)
                 outs += [a_all, const]
-                grads += [e["ga"], e["gconst"]]
-                a_prev = a_all
-            torch.autograd.backward(outs, [g.clone() for g in grads])
-        for e in self.levels:
-            e["ga"].zero_()
-            e["gconst"].zero_()
-        self.pending = False
+            torch.autograd.backward(outs, [g.clone() for e in self.levels for g in (e.ga, e.gconst)])
+        self.drop_accumulated()
 
 
 class Deferred:
@@ -408,33 +404,35 @@ class Deferred:
             store[lv] = torch.empty(self.tile.B * r * r, self.off[-1], dtype=torch.float32, device=self.tile.device)
         return store[lv]
 
+    def sums(self, src, lv):
+        """Source ``src``'s column block of the sum matrix of ALTO level ``lv``."""
+        return self._matrix(self.S, lv)[:, self.off[src]:self.off[src + 1]]
+
     def grad_matrix(self, lv):
         return self._matrix(self.dS, lv), self.dS_cols.get(lv, 0)
 
     def write_sums(self, src, rows):
         """Per-cell sums of ``rows`` [N, K_src] into the source's column block at every needed resolution: the finest from the
         rows (read once), the coarser ones by 2x2 pooling."""
-        lo, hi = self.off[src], self.off[src + 1]
-        levels = self.needed(src)
-        _segsum_into(self.tile, rows, levels[0], self._matrix(self.S, levels[0])[:, lo:hi])
+        finest = self.needed(src)[0]
+        _segsum_into(self.tile, rows, finest, self.sums(src, finest))
         self.pool_down(src)
 
     def pool_down(self, src, start=0):
         """The source's sums at its coarser needed resolutions from the (already written) finest one, by 2x2 pooling;
         ``start``: index of the coarsest needed resolution that is written already."""
-        tile, (lo, hi) = self.tile, (self.off[src], self.off[src + 1])
         levels = self.needed(src)
         cur_level = levels[start]
-        cur = self._matrix(self.S, cur_level)[:, lo:hi]
+        cur = self.sums(src, cur_level)
         for lv in levels[start + 1:]:
             while cur_level < lv:
                 nxt_level = cur_level + 1
                 if nxt_level in levels:
-                    nxt = self._matrix(self.S, nxt_level)[:, lo:hi]
+                    nxt = self.sums(src, nxt_level)
                 else:                                       # a resolution no level uses: a compact temporary on the way down
-                    rn = tile.R >> nxt_level
-                    nxt = torch.empty(tile.B * rn * rn, hi - lo, dtype=torch.float32, device=tile.device)
-                _sumpool_into(tile, cur, cur_level, nxt)
+                    rn = self.tile.R >> nxt_level
+                    nxt = torch.empty(self.tile.B * rn * rn, cur.shape[1], dtype=torch.float32, device=cur.device)
+                _sumpool_into(self.tile, cur, cur_level, nxt)
                 cur, cur_level = nxt, nxt_level
 
     def hidden_grad(self, planes, h, r, c2, mask_is_bits=False):
@@ -463,23 +461,19 @@ class Deferred:
         idx = self.n_done
         if self.tile.level(r) != self.levels_seq[idx]:
             raise RuntimeError("deferred levels out of order")
-        wc, bc, w1, b1 = fc_c.weight, fc_c.bias, fc_b.weight, fc_b.bias
+        params = (fc_c.weight, fc_c.bias, fc_b.weight, fc_b.bias)
         if self.cache is not None:                          # weights-only work shared by all tiles of an optimizer step
-            a_all, const = self.cache.get(idx, (wc, bc, w1, b1))
-            raster, _ = _DeferredLevel.apply(q_rows, a_all, const, self.base if idx == 0 else None, self, idx, r)
-            self.n_done += 1
-            return raster
-        self.a_all = _ComposeStack.apply(self.a_all, wc, w1)
-        if self.const is None:
-            self.const = (bc + b1).reshape(1, -1)
+            a_all, const = self.cache.get(idx, params)
         else:
-            self.const = mlp.linear(self.const, wc, bc) + b1.reshape(1, -1)   # const_k = const_{k-1} Wc_k^T + bc_k + b1_k
-        raster, self.a_all = _DeferredLevel.apply(q_rows, self.a_all, self.const, self.base if idx == 0 else None, self, idx, r)
+            a_all, const = self.a_all, self.const = _compose_step(self.a_all, self.const, params)
+        raster, a_thru = _DeferredLevel.apply(q_rows, a_all, const, self.base if idx == 0 else None, self, idx, r)
         self.n_done += 1
-        if self.n_done == len(self.levels_seq):
-            # last level: nobody composes further.  (Also breaks the cycle state -> a_all -> its autograd node -> state, which
-            # would leave the sum matrices of every step to the cyclic garbage collector.)
-            self.a_all = self.const = None
+        if self.cache is None:
+            # the maps go on to the next level's compose product (_DeferredLevel._finish); after the last level nobody composes
+            # further.  (That also breaks the cycle state -> a_all -> its autograd node -> state, which would leave the sum
+            # matrices of every step to the cyclic garbage collector.)
+            last = self.n_done == len(self.levels_seq)
+            self.a_all, self.const = (None, None) if last else (a_thru, const)
         return raster
 
 

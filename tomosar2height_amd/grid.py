@@ -355,7 +355,7 @@ def _param_grad_targets(weight, bias):
     (the trainer's bucket) under ``mlp.direct_grad_accumulation`` when their layout allows it (``direct``: the autograd function
     then returns None for them), else fresh tensors to be written."""
     wg = weight.grad
-    if mlp._DIRECT_ACCUM and wg is not None and wg.permute(0, 2, 3, 1).is_contiguous():
+    if mlp.direct_accum() and wg is not None and wg.permute(0, 2, 3, 1).is_contiguous():
         if bias is None:
             return wg, None, True
         bg = bias.grad
@@ -405,7 +405,7 @@ def _conv3x3_param_grads(gm, x, weight, bias):
     ``mlp.direct_grad_accumulation`` -- returns (None, None) then -- else as fresh tensors."""
     dw, db, direct = _param_grad_targets(weight, bias)
     if direct:
-        side = mlp._CONV_WGRAD_STREAM
+        side = mlp.conv_wgrad_stream()
         if side is not None and x.shape[2] * x.shape[3] <= OVERLAP_MAX_PIXELS:
             # small planes: the weight gradient (off the backward's critical path: nothing reads the bucket before the
             # optimizer step) runs on a side stream beside the next layers' data gradients -- these launches are
@@ -661,7 +661,7 @@ class _UpConv2x2(torch.autograd.Function):
         dw, db, direct = _param_grad_targets(weight, bias)
         # like the 3x3 weight gradients on the trainer's side stream when there is one (_conv3x3_param_grads) -- unless g is also
         # handed on as the addend's gradient: its consumer may accumulate into it in place on the main stream (mlp.sole_owner)
-        side = mlp._CONV_WGRAD_STREAM if (direct and not ctx.has_addend) else None
+        side = mlp.conv_wgrad_stream() if (direct and not ctx.has_addend) else None
         with mlp.fork_to(side) if side is not None else contextlib.nullcontext():
             upconv2x2_wgrad_(g, ldg, x, dw, db, wgrad_bx3, accumulate=direct, defer=direct)
         if side is not None:
@@ -708,7 +708,7 @@ def _head_bwd(xs, dxs, weight, bias, g, relu_inputs=()):
     # r05: this head was the last layer whose gradients still went through autograd's AccumulateGrad (two adds per tile, and in the
     # tile pipeline a hop to the stream the accumulator node was created on)
     wg, bg = weight.grad, (bias.grad if bias is not None else None)
-    direct = (mlp._DIRECT_ACCUM and wg is not None and wg.is_contiguous() and wg.numel() == ctot
+    direct = (mlp.direct_accum() and wg is not None and wg.is_contiguous() and wg.numel() == ctot
               and (bias is None or (bg is not None and bg.is_contiguous())))
     if direct:
         dw, db = wg, bg

@@ -8,12 +8,15 @@ and the reference's ``torch.cat([net, pooled], dim=2)`` (pointnet.py:78) never m
 writes its output into the left half of the next block's [M, 2h] input buffer and ``pool_max`` writes the right
 half in place.  There is no CPU path here: all tensors must live on the device.
 """
+import contextlib
+import ctypes
 import os
 from typing import Optional
 
 import torch
 
-from . import _lib
+from . import _lib, ops
+from .ops import _rows, pool_max_fwd_ as _pool_fwd_        # (_pool_fwd_: the name tests launch the pooling by)
 
 
 # ------------------------------------------------------------------------------------------------ precision
@@ -48,17 +51,6 @@ def _pflag() -> int:
 
 
 # ------------------------------------------------------------------------------------------------ kernel calls
-def _rows(t: torch.Tensor, what: str):
-    """A 2-D fp32 device view whose rows are contiguous (row stride >= width): returns (ptr, ld)."""
-    if t.dim() != 2 or t.dtype != torch.float32 or (t.shape[1] > 1 and t.stride(1) != 1):
-        raise ValueError(f"{what}: expected a 2-D float32 tensor with unit inner stride, got {tuple(t.shape)} "
-                         f"strides {t.stride()}")
-    if not t.is_cuda:
-        raise RuntimeError(f"{what}: expected device tensors; tomosar2height_amd has no CPU path "
-                           "(the CPU restatement lives in oracle/ for tests only)")
-    return t.data_ptr(), (t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1]))
-
-
 # Grid-side products of the deferred point update (deferred.py) on the bf16 matrix cores with the exact 3-way split
 # (csrc/conv_bx3.hip, 1-tap form; fp32-grade like the convolutions): T2H_GEMM_BX3=0 keeps them on the fp32 MFMA kernels (A/B)
 GEMM_BX3 = os.environ.get("T2H_GEMM_BX3", "1") != "0"
@@ -81,8 +73,7 @@ def _bx3_gemm_ok(m, k, n, *rows, force=False) -> bool:
     (the r = 256 level product 2752 -> 64: 250 us on fp32 MFMA, 278 us split); with the fp16 two-way split and the weights fetched
     straight into registers (r04d) it is 197 us (profiles/gemm_layout_probe.py), so 64 outputs are in (r05: the threshold itself had
     stayed at 128; at 64 the data gradient of the stacked per-pixel product, 2752 -> 64 over 65 536 rows, goes from 245 to 208 us).
-    One-chunk reductions that
-    only WRITE a wide matrix (64 -> 2752: 274 us split against 247 us) stay on the fp32 kernels."""
+    One-chunk reductions that only WRITE a wide matrix (64 -> 2752: 274 us split against 247 us) stay on the fp32 kernels."""
     if not (GEMM_BX3 and _MODE == "fp32" and bool(_lib.ws_bytes("t2h_gemm_bx3_supported", m, k, n))
             and all(t is None or (t.stride(0) % 4 == 0 and t.data_ptr() % 16 == 0) for t in rows)):
         return False
@@ -159,56 +150,35 @@ def linear_wgrad_(dy, x, dw, db, relu_in=False, accumulate=False, defer=False):
             if db is not None:
                 db.zero_()
         return
-    if (_GEMM_BX3_WGRAD and GEMM_BX3 and _MODE == "fp32" and not relu_in and n >= _BX3_WGRAD_MIN_N and m >= _BX3_WGRAD_MIN_M
-            and _grid_h2() and bool(_lib.ws_bytes("t2h_gemm_bx3_wgrad_supported", m, k, n))):
-        # r06: the wide grid-side products' weight gradients (the per-resolution sum matrices of the deferred update: N = 2368 ..
-        # 2752 columns, K = 64 .. 256) on the split kernels -- fp32-grade products from three fp16 MFMAs like their forward and data
-        # gradient (bx3_wgrad_kernel<.., GT = K / 32>; T2H_GEMM_BX3_WGRAD=1)
-        ws_bytes = _lib.ws_bytes("t2h_gemm_bx3_wgrad_workspace_bytes", m, k, n)
-        ws = _lib.workspace(ws_bytes, dy.device)
-        flags = (_lib.ACCUM if accumulate else 0) | _lib.F16X2 | (_lib.defer_reduce(ws, dw) if defer else 0)
-        _lib.call("t2h_gemm_bx3_wgrad", gp, ldg, xp, ldx, m, k, n, dw.data_ptr(), db.data_ptr() if db is not None else None, flags,
-                  ws.data_ptr(), ws_bytes, _lib.stream(), nbytes=4 * (m * k + m * n + n * k), flops=2 * m * k * n,
-                  tag=_lib.timing() and f"t2h_linear_wgrad[N={n},K={k}]")
-        return
-    ws_bytes = _lib.ws_bytes("t2h_linear_wgrad_workspace_bytes", m, k, n)
+    # r06: the wide grid-side products' weight gradients (the per-resolution sum matrices of the deferred update: N = 2368 ..
+    # 2752 columns, K = 64 .. 256) on the split kernels -- fp32-grade products from three fp16 MFMAs like their forward and data
+    # gradient (bx3_wgrad_kernel<.., GT = K / 32>; T2H_GEMM_BX3_WGRAD=1)
+    bx3 = (_GEMM_BX3_WGRAD and GEMM_BX3 and _MODE == "fp32" and not relu_in and n >= _BX3_WGRAD_MIN_N and m >= _BX3_WGRAD_MIN_M
+           and _grid_h2() and bool(_lib.ws_bytes("t2h_gemm_bx3_wgrad_supported", m, k, n)))
+    query, pflags = (("t2h_gemm_bx3_wgrad_workspace_bytes", _lib.F16X2) if bx3 else
+                     ("t2h_linear_wgrad_workspace_bytes", (_lib.RELU_IN if relu_in else 0) | _pflag()))
+    ws_bytes = _lib.ws_bytes(query, m, k, n)
     ws = _lib.workspace(ws_bytes, dy.device)
-    flags = (_lib.RELU_IN if relu_in else 0) | (_lib.ACCUM if accumulate else 0) | _pflag() | (_lib.defer_reduce(ws, dw) if defer else 0)
-    _lib.call("t2h_linear_wgrad", gp, ldg, xp, ldx, m, k, n, flags, dw.data_ptr(), db.data_ptr() if db is not None else None,
-              ws.data_ptr(), ws_bytes, _lib.stream(), nbytes=4 * (m * k + m * n + n * k), flops=2 * m * k * n,
-              tag=_lib.timing() and f"t2h_linear_wgrad[N={n},K={k}]")
+    flags = pflags | (_lib.ACCUM if accumulate else 0) | (_lib.defer_reduce(ws, dw) if defer else 0)
+    outs = (dw.data_ptr(), db.data_ptr() if db is not None else None)
+    cost = dict(nbytes=4 * (m * k + m * n + n * k), flops=2 * m * k * n, tag=_lib.timing() and f"t2h_linear_wgrad[N={n},K={k}]")
+    if bx3:
+        _lib.call("t2h_gemm_bx3_wgrad", gp, ldg, xp, ldx, m, k, n, *outs, flags, ws.data_ptr(), ws_bytes, _lib.stream(), **cost)
+    else:
+        _lib.call("t2h_linear_wgrad", gp, ldg, xp, ldx, m, k, n, flags, *outs, ws.data_ptr(), ws_bytes, _lib.stream(), **cost)
 
 
-_DIRECT_ACCUM = False
-_WGRAD_STREAM = None
-_CONV_WGRAD_STREAM = None        # side stream for the convolution weight gradients (grid._conv3x3_param_grads)
-_MAIN_STREAM = None              # torch's current stream when the block was entered (what the side streams fork from)
-
-
-_HELD = []                       # tensors read by side-stream launches of the current pass: released after the streams have joined
-
-
-def hold(*tensors):
-    """Keep ``tensors`` (inputs of a launch on a side stream) alive until the pass's streams have joined
-    (``direct_grad_accumulation.__exit__``), instead of ``record_stream``: the caching allocator then sees every free in the main
-    stream's order -- no per-block event bookkeeping, no blocks parked behind unfinished side-stream work (with 8 tiles per
-    micro-batch the parked blocks made the allocator grow mid-run: 5.7 vs 13 ms per tile, run to run)."""
-    _HELD.extend(tensors)
-
-
-def fork_to(side):
-    """Order ``side`` behind everything issued so far on the stream the backward pass runs on, then launch there:
-    ``with mlp.fork_to(side): ...`` (``_lib.on_stream``: the cheap form of ``torch.cuda.stream``)."""
-    main = _MAIN_STREAM if _MAIN_STREAM is not None else torch.cuda.current_stream()
-    side.wait_stream(main)
-    return _lib.on_stream(side, main)
-
-
+# ------------------------------------------------------------------------------------------------ backward-pass state
 class direct_grad_accumulation:
     """While active, weight/bias gradients of the per-point layers are accumulated by the wgrad kernel straight into
     an existing contiguous ``param.grad`` (e.g. the Trainer's flat bucket views) and the autograd Function returns
     ``None`` for them -- this removes one elementwise add launch per parameter per tile.  Off by default so that
-    ``torch.autograd.grad`` and first-touch (``grad is None``) semantics stay the standard ones."""
+    ``torch.autograd.grad`` and first-touch (``grad is None``) semantics stay the standard ones.
+
+    The active block is also the record of the pass's state (``_PASS``).  ``main_stream``: torch's current stream when the
+    outermost block with a side stream was entered (what the side streams fork from).  ``held``: tensors read by side-stream
+    launches, released after the streams have joined -- ONE list for the process, handed from block to block."""
+    __slots__ = ("enabled", "side_stream", "conv_side_stream", "main_stream", "held", "prev")
 
     def __init__(self, enabled: bool = True, side_stream=None, conv_side_stream=None):
         """``side_stream``: issue the accumulating weight-gradient GEMMs there.  They are off the backward's critical
@@ -218,40 +188,63 @@ class direct_grad_accumulation:
         self.enabled = enabled
         self.side_stream = side_stream if enabled else None
         self.conv_side_stream = conv_side_stream if enabled else None
+        self.main_stream, self.held = None, []
 
     def __enter__(self):
-        global _DIRECT_ACCUM, _WGRAD_STREAM, _CONV_WGRAD_STREAM, _MAIN_STREAM
-        self.prev, _DIRECT_ACCUM = _DIRECT_ACCUM, self.enabled
-        self.prev_stream, _WGRAD_STREAM = _WGRAD_STREAM, self.side_stream
-        self.prev_conv_stream, _CONV_WGRAD_STREAM = _CONV_WGRAD_STREAM, self.conv_side_stream
-        self.prev_main = _MAIN_STREAM
+        global _PASS
+        self.prev, _PASS = _PASS, self
+        self.main_stream, self.held = self.prev.main_stream, self.prev.held
         if self.side_stream is not None or self.conv_side_stream is not None:
-            _MAIN_STREAM = torch.cuda.current_stream()          # (once per pass: the autograd engine runs the backward on it)
+            self.main_stream = torch.cuda.current_stream()      # (once per pass: the autograd engine runs the backward on it)
         return self
 
     def __exit__(self, *exc):
-        global _DIRECT_ACCUM, _WGRAD_STREAM, _CONV_WGRAD_STREAM, _MAIN_STREAM
-        if _MAIN_STREAM is not None and self.prev_main is None:
+        global _PASS
+        if self.main_stream is not None and self.prev.main_stream is None:
             # join: afterwards the gradients are visible in stream order on the main stream like any other result, and what the
             # side-stream launches read may be recycled
             for st in {id(s): s for s in (self.side_stream, self.conv_side_stream) if s is not None}.values():
-                _MAIN_STREAM.wait_stream(st)
-            _HELD.clear()
-        _DIRECT_ACCUM = self.prev
-        _WGRAD_STREAM = self.prev_stream
-        _CONV_WGRAD_STREAM = self.prev_conv_stream
-        _MAIN_STREAM = self.prev_main
+                self.main_stream.wait_stream(st)
+            self.held.clear()
+        _PASS = self.prev
+
+
+_PASS = direct_grad_accumulation(False)          # outside any block: nothing direct, no side streams
+
+
+def direct_accum() -> bool:
+    """True inside ``direct_grad_accumulation(True)``: parameter gradients may be accumulated straight into ``param.grad``."""
+    return _PASS.enabled
+
+
+def conv_wgrad_stream():
+    """The side stream of the convolution weight gradients (grid._conv3x3_param_grads), or None."""
+    return _PASS.conv_side_stream
+
+
+def hold(*tensors):
+    """Keep ``tensors`` (inputs of a launch on a side stream) alive until the pass's streams have joined
+    (``direct_grad_accumulation.__exit__``), instead of ``record_stream``: the caching allocator then sees every free in the main
+    stream's order -- no per-block event bookkeeping, no blocks parked behind unfinished side-stream work (with 8 tiles per
+    micro-batch the parked blocks made the allocator grow mid-run: 5.7 vs 13 ms per tile, run to run)."""
+    _PASS.held.extend(tensors)
+
+
+def fork_to(side):
+    """Order ``side`` behind everything issued so far on the stream the backward pass runs on, then launch there:
+    ``with mlp.fork_to(side): ...`` (``_lib.on_stream``: the cheap form of ``torch.cuda.stream``)."""
+    main = _PASS.main_stream if _PASS.main_stream is not None else torch.cuda.current_stream()
+    side.wait_stream(main)
+    return _lib.on_stream(side, main)
 
 
 def _wgrad(dy, x, w, bias, relu_in=False):
-    if (_DIRECT_ACCUM and w.shape[0] % 4 == 0 and w.grad is not None and w.grad.is_contiguous()
+    if (_PASS.enabled and w.shape[0] % 4 == 0 and w.grad is not None and w.grad.is_contiguous()
             and (bias is None or (bias.grad is not None and bias.grad.is_contiguous()))):
-        side = _WGRAD_STREAM
-        if side is None:
+        side = _PASS.side_stream
+        with fork_to(side) if side is not None else contextlib.nullcontext():       # dy / x are produced on the main stream
             linear_wgrad_(dy, x, w.grad, None if bias is None else bias.grad, relu_in=relu_in, accumulate=True, defer=True)
-        else:
-            with fork_to(side):                                     # dy / x are produced on the main stream
-                linear_wgrad_(dy, x, w.grad, None if bias is None else bias.grad, relu_in=relu_in, accumulate=True, defer=True)
+        if side is not None:
             hold(dy, x)                                             # keep the allocator from recycling them early
         return None, None
     if w.shape[0] % 4 != 0:
@@ -264,39 +257,6 @@ def _wgrad(dy, x, w, bias, relu_in=False):
     db = torch.empty_like(bias) if bias is not None else None
     linear_wgrad_(dy, x, dw, db, relu_in=relu_in)
     return dw, db
-
-
-def _pool_rows_ok(c, *lds):
-    """The row-balanced pooling kernels (t2h_pool_rows_*) serve 16-byte rows of up to 64 channels."""
-    return c % 4 == 0 and c <= 64 and all(ld % 4 == 0 for ld in lds)
-
-
-def _pool_fwd_(tile, feat, pooled, winner):
-    (fp, ldf), (pp, ldp) = _rows(feat, "pool feat"), _rows(pooled, "pool out")
-    c = feat.shape[1]
-    # forward: the cell-parallel kernel is the faster one (13 vs 24 us at the bench shape); backward: the row-balanced one
-    _lib.call("t2h_pool_max_fwd", fp, ldf, _lib.ptr(tile.off0), tile.B, tile.nbits, c, pp, ldp, _lib.ptr(winner),
-              _lib.stream(), nbytes=8 * c * tile.n_points + 4 * tile.n_points)
-
-
-def _pool_bwd_(tile, gpooled, winner, gfeat, accumulate):
-    (gp, ldg), (op, ldo) = _rows(gpooled, "pool gpooled"), _rows(gfeat, "pool gfeat")
-    c = gpooled.shape[1]
-    nbytes = 8 * c * tile.n_points + 4 * tile.n_points
-    if _pool_rows_ok(c, ldg, ldo):
-        _lib.call("t2h_pool_rows_bwd", gp, ldg, _lib.ptr(winner), _lib.ptr(tile.cell), _lib.ptr(tile.off0), tile.n_points, c,
-                  1 if accumulate else 0, op, ldo, _lib.stream(), nbytes=nbytes, tag="t2h_pool_max_bwd")
-    else:
-        _lib.call("t2h_pool_max_bwd", gp, ldg, _lib.ptr(winner), _lib.ptr(tile.off0), tile.B, tile.nbits, c,
-                  1 if accumulate else 0, op, ldo, _lib.stream(), nbytes=nbytes)
-
-
-def _pool_mean_(tile, src, dst, accumulate):
-    """dst (=|+=) per-cell mean of src, scatter_type='mean' (pointnet.py:55-56); its own adjoint, so also the backward."""
-    (sp, lds), (dp, ldd) = _rows(src, "pool src"), _rows(dst, "pool dst")
-    c = src.shape[1]
-    _lib.call("t2h_pool_mean", sp, lds, _lib.ptr(tile.off0), tile.B, tile.nbits, c, 1 if accumulate else 0, dp, ldd,
-              _lib.stream(), nbytes=(8 + (4 if accumulate else 0)) * c * tile.n_points + 4 * tile.n_points)
 
 
 def _empty(rows, cols, like):
@@ -331,12 +291,10 @@ class _Linear(torch.autograd.Function):
                 dx = gy @ w
                 if ctx.relu_in:
                     dx = dx * (x > 0)
-        dw, db = _wgrad(gy, x, w, bias, relu_in=ctx.relu_in)
-        return dx, dw, db, None
+        return (dx, *_wgrad(gy, x, w, bias, relu_in=ctx.relu_in), None)
 
 
 def _linear1_backward(ctx, x, w, bias, gy):
-    import ctypes
     m, k = x.shape
     a = x
     if ctx.relu_in:                                    # the head kernels take the ReLU OUTPUT: a = x * (x > 0), one pass
@@ -380,7 +338,6 @@ def _join_plane_grad(dy, w, gthru, shape_nhwc, was_cl):
     """dplane = dy w (rows -> the NHWC plane) + gthru: the gradient of the plane's other consumers joins inside the data-gradient
     kernel (accumulating epilogue) where it arrives as a dense NHWC tensor that nobody else still reads (``sole_owner``), else
     by one add into a fresh tensor."""
-    from . import ops
     b, r1, r2, c = shape_nhwc
     if (gthru is not None and gthru.dtype == torch.float32 and gthru.permute(0, 2, 3, 1).is_contiguous() and was_cl
             and sole_owner(gthru)):
@@ -400,7 +357,6 @@ class _LinearPlaneThru(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, plane, w, bias):
-        from . import ops
         ctx.was_cl = ops._is_channels_last(plane)
         p = ops.to_nhwc(plane)
         _lib.require_device(p, what="linear_plane_thru")
@@ -421,8 +377,7 @@ class _LinearPlaneThru(torch.autograd.Function):
         dplane = gthru
         if ctx.needs_input_grad[0]:
             dplane = _join_plane_grad(gq, w, gthru, ctx.shape, ctx.was_cl)
-        dw, db = _wgrad(gq, rows, w, bias)
-        return dplane, dw, db
+        return (dplane, *_wgrad(gq, rows, w, bias))
 
 
 def linear_plane_thru(plane, weight, bias):
@@ -471,8 +426,7 @@ class _ResBlock(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         x, hr, w0, b0, w1, b1, ws = ctx.saved_tensors
-        dx, dw0, db0, dw1, db1, dws = _resblock_bwd(gy.contiguous(), x, hr, w0, b0, w1, b1, ws, ctx.needs_input_grad[0])
-        return dx, dw0, db0, dw1, db1, dws
+        return _resblock_bwd(gy.contiguous(), x, hr, w0, b0, w1, b1, ws, ctx.needs_input_grad[0])
 
 
 def resblock(x: torch.Tensor, w0, b0, w1, b1, ws) -> torch.Tensor:
@@ -483,35 +437,51 @@ def resblock(x: torch.Tensor, w0, b0, w1, b1, ws) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------------ ALTO point update
+def _comm_tail_fwd(ctx, h, c_last, wb, bb, wc, bc):
+    """c = fc_comm.2(h) + fc_c(c_last): everything behind the hidden activations, the same in both forms of the update."""
+    out = _empty(h.shape[0], wb.shape[0], h)
+    linear_fwd_(h, wb, bb, out)
+    if c_last is not None:
+        linear_fwd_(c_last, wc, bc, out, accumulate=True)
+    ctx.has_last = c_last is not None
+    return out
+
+
+def _comm_tail_bwd(ctx, g, h, c_last, wb, bb, wc, bc, hidden_bwd):
+    """Its backward.  ``hidden_bwd(dh)``: the form's own way from the masked hidden gradient back to its input, issued between
+    fc_comm.2's launches and fc_c's.  Returns (what ``hidden_bwd`` returned, dlast, dwb, dbb, dwc, dbc)."""
+    dwb, dbb = _wgrad(g, h, wb, bb)
+    dh = linear_dgrad_(g, wb, torch.empty_like(h), mask=h)                  # through fc_comm.2 and the ReLU
+    front = hidden_bwd(dh)
+    dlast = dwc = dbc = None
+    if ctx.has_last:
+        dwc, dbc = _wgrad(g, c_last, wc, bc)
+        if ctx.needs_input_grad[1]:
+            dlast = linear_dgrad_(g, wc, torch.empty_like(c_last))
+    return front, dlast, dwb, dbb, dwc, dbc
+
+
 class _CommMLP(torch.autograd.Function):
     """c = fc_comm.2(relu(fc_comm.0(sampled))) + fc_c(c_last)   (alto.py:121-128, 245-253)."""
 
     @staticmethod
     def forward(ctx, sampled, c_last, wa, ba, wb, bb, wc, bc):
-        m = sampled.shape[0]
-        h = _empty(m, wa.shape[0], sampled)
+        h = _empty(sampled.shape[0], wa.shape[0], sampled)
         linear_fwd_(sampled, wa, ba, h, relu_out=True)
-        out = _empty(m, wb.shape[0], sampled)
-        linear_fwd_(h, wb, bb, out)
-        if c_last is not None:
-            linear_fwd_(c_last, wc, bc, out, accumulate=True)
-        ctx.has_last = c_last is not None
+        out = _comm_tail_fwd(ctx, h, c_last, wb, bb, wc, bc)
         ctx.save_for_backward(sampled, c_last, h, wa, ba, wb, bb, wc, bc)
         return out
 
     @staticmethod
     def backward(ctx, g):
         sampled, c_last, h, wa, ba, wb, bb, wc, bc = ctx.saved_tensors
-        g = g.contiguous()
-        dwb, dbb = _wgrad(g, h, wb, bb)
-        dh = linear_dgrad_(g, wb, torch.empty_like(h), mask=h)
-        dwa, dba = _wgrad(dh, sampled, wa, ba)
-        ds = linear_dgrad_(dh, wa, torch.empty_like(sampled)) if ctx.needs_input_grad[0] else None
-        dlast = dwc = dbc = None
-        if ctx.has_last:
-            dwc, dbc = _wgrad(g, c_last, wc, bc)
-            if ctx.needs_input_grad[1]:
-                dlast = linear_dgrad_(g, wc, torch.empty_like(c_last))
+
+        def hidden_bwd(dh):
+            dwa, dba = _wgrad(dh, sampled, wa, ba)
+            ds = linear_dgrad_(dh, wa, torch.empty_like(sampled)) if ctx.needs_input_grad[0] else None
+            return ds, dwa, dba
+
+        (ds, dwa, dba), dlast, dwb, dbb, dwc, dbc = _comm_tail_bwd(ctx, g.contiguous(), h, c_last, wb, bb, wc, bc, hidden_bwd)
         return ds, dlast, dwa, dba, dwb, dbb, dwc, dbc
 
 
@@ -544,10 +514,7 @@ def hidden_from_plane(tile, plane_rows, r, w_a, b_a):
     q = _empty(plane_rows.shape[0], w_a.shape[0], plane_rows)
     linear_fwd_(plane_rows, w_a, b_a, q)                                       # fc_comm.0 on the pixels
     h = _empty(tile.n_points, w_a.shape[0], plane_rows)
-    c2 = w_a.shape[0]
-    _lib.call("t2h_sample_fwd_relu", _lib.ptr(q), _lib.ptr(tile.pts), tile.dim, tile.B, tile.N, r, c2, _lib.ptr(h), None,
-              _lib.stream(), nbytes=4 * c2 * tile.n_points + 8 * tile.n_points + 4 * q.numel(),
-              tag=_lib.timing() and f"t2h_sample_fwd_relu[C={c2},r={r}]")
+    ops.sample_fwd_relu_(tile, q, r, h)
     return h
 
 
@@ -558,44 +525,33 @@ class _CommMLPGridFirst(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, plane, c_last, wa, ba, wb, bb, wc, bc, tile):
-        from . import ops
         ctx.was_cl = ops._is_channels_last(plane)
         p = ops.to_nhwc(plane)
         _lib.require_device(p, what="comm_mlp_grid_first")
         b, r, _, c = p.shape
         rows = p.reshape(b * r * r, c)
         h = hidden_from_plane(tile, rows, r, wa, ba)
-        out = _empty(tile.n_points, wb.shape[0], rows)
-        linear_fwd_(h, wb, bb, out)
-        if c_last is not None:
-            linear_fwd_(c_last, wc, bc, out, accumulate=True)
-        ctx.has_last = c_last is not None
+        out = _comm_tail_fwd(ctx, h, c_last, wb, bb, wc, bc)
         ctx.tile, ctx.r = tile, r
         ctx.save_for_backward(rows, c_last, h, wa, ba, wb, bb, wc, bc)
         return out, ops._alias(plane)
 
     @staticmethod
     def backward(ctx, g, gthru):
-        from . import ops
         rows, c_last, h, wa, ba, wb, bb, wc, bc = ctx.saved_tensors
         tile, r = ctx.tile, ctx.r
         if g is None:
             return gthru, None, None, None, None, None, None, None, None
-        g = g.contiguous()
-        dwb, dbb = _wgrad(g, h, wb, bb)
-        dh = linear_dgrad_(g, wb, torch.empty_like(h), mask=h)                  # through fc_comm.2 and the ReLU
-        dq = ops._sample_bwd(tile, dh, r, h.shape[1], None).reshape(rows.shape[0], h.shape[1])    # S^T dh: [B r r, 2C]
-        dwa, dba = _wgrad(dq, rows, wa, ba)                                     # column sums of dq == of dh (taps sum to 1)
-        dplane = None
-        if ctx.needs_input_grad[0]:
-            dplane = _join_plane_grad(dq, wa, gthru, (tile.B, r, r, rows.shape[1]), ctx.was_cl)
-        elif gthru is not None:
+
+        def hidden_bwd(dh):
+            dq = ops._sample_bwd(tile, dh, r, h.shape[1], None).reshape(rows.shape[0], h.shape[1])    # S^T dh: [B r r, 2C]
+            dwa, dba = _wgrad(dq, rows, wa, ba)                                 # column sums of dq == of dh (taps sum to 1)
             dplane = gthru
-        dlast = dwc = dbc = None
-        if ctx.has_last:
-            dwc, dbc = _wgrad(g, c_last, wc, bc)
-            if ctx.needs_input_grad[1]:
-                dlast = linear_dgrad_(g, wc, torch.empty_like(c_last))
+            if ctx.needs_input_grad[0]:
+                dplane = _join_plane_grad(dq, wa, gthru, (tile.B, r, r, rows.shape[1]), ctx.was_cl)
+            return dplane, dwa, dba
+
+        (dplane, dwa, dba), dlast, dwb, dbb, dwc, dbc = _comm_tail_bwd(ctx, g.contiguous(), h, c_last, wb, bb, wc, bc, hidden_bwd)
         return dplane, dlast, dwa, dba, dwb, dbb, dwc, dbc, None
 
 
@@ -608,16 +564,37 @@ def comm_mlp_grid_first(tile, plane, w_a, b_a, w_b, b_b, c_last, w_c, b_c):
 FUSED_TRUNK = os.environ.get("T2H_FUSED_TRUNK", "1") != "0"      # A/B switch: 0 = one GEMM launch per Linear + pool kernels
 
 
-def _fused_trunk_applicable(pts, params, n_blocks) -> bool:
+def _split_params(params):
+    """The trunk's flat weights (w_pos, b_pos, [w0, b0, w1, b1, ws] * n_blocks, w_c, b_c) -> (w_pos, b_pos, blocks, w_c, b_c)."""
+    return params[0], params[1], [params[i: i + 5] for i in range(2, len(params) - 2, 5)], params[-2], params[-1]
+
+
+def _join_grads(pos, blocks, c):
+    """The inverse for the gradients: (dw_pos, db_pos), one 5-list per block, (dw_c, db_c) -> a list in ``params`` order."""
+    return [*pos, *[g for blk in blocks for g in blk], *c]
+
+
+def _pack_fused(nets, pooled, hrs, winners):
+    """What the fused forward leaves for its backward, as one flat tuple for ``save_for_backward``."""
+    return (*nets, *pooled[1:], *hrs, *winners)
+
+
+def _unpack_fused(rest, nb):
+    """-> (nets, pooled, hrs, winners) of ``_pack_fused``: the first block has no pooled input and no winner bits."""
+    cuts = (0, nb, 2 * nb - 1, 3 * nb - 1, len(rest))
+    nets, pooled, hrs, winners = (rest[lo:hi] for lo, hi in zip(cuts, cuts[1:]))
+    return nets, [None, *pooled], hrs, winners
+
+
+def _fused_trunk_applicable(pts, w_pos, blocks, w_c) -> bool:
     """The fused block kernel (csrc/trunk.hip) is built for the reference's trunk widths: hidden_dim = 32, i.e.
     fc_pos 3 -> 64, blocks 64 -> 32 with a shortcut, fc_c 32 -> 32 (tomosar2height.yaml:7-8, pointnet.py:36-40)."""
-    if not FUSED_TRUNK or n_blocks < 2 or pts.shape[1] < 3 or tuple(params[0].shape) != (64, 3):
+    if not FUSED_TRUNK or len(blocks) < 2 or pts.shape[1] < 3 or tuple(w_pos.shape) != (64, 3):
         return False
-    for i in range(n_blocks):
-        w0, b0, w1, b1, ws = params[2 + 5 * i: 7 + 5 * i]
+    for w0, b0, w1, b1, ws in blocks:
         if ws is None or tuple(w0.shape) != (32, 64) or tuple(w1.shape) != (32, 32) or tuple(ws.shape) != (32, 64):
             return False
-    return tuple(params[-2].shape) == (32, 32)
+    return tuple(w_c.shape) == (32, 32)
 
 
 # r06: the whole trunk forward in one launch (t2h_trunk_fused_fwd, bit-identical to one launch per block).  With one scan per cell in
@@ -632,12 +609,11 @@ _TRUNK_UNIT_BOUNDS = os.environ.get("T2H_TRUNK_UNIT_BOUNDS", "1") != "0"     # g
 
 def _trunk_forward_one_launch(tile, pts, w_pos, b_pos, blocks, w_c, b_c):
     """pointnet.py:72-82 as ONE launch: same return value as the per-block form."""
-    import ctypes
     m, nb, dev = pts.shape[0], len(blocks), pts.device
     hrs = [_empty(m, 32, pts) for _ in range(nb)]
     nets = [_empty(m, 32, pts) for _ in range(nb)]
     pooled = [None] + [_empty(m, 32, pts) for _ in range(nb - 1)]
-    winners = [torch.empty(m, 8, dtype=torch.uint8, device=dev) for _ in range(nb - 1)]
+    winners = [ops.winner_bits(m, 32, dev) for _ in range(nb - 1)]
     c_out = _empty(m, 32, pts)
     keep = [t.contiguous() for blk in blocks for t in blk] + [w_pos.contiguous(), w_c.contiguous()]
     arr = ctypes.c_void_p * nb
@@ -670,7 +646,7 @@ def _trunk_forward_fused(tile, pts, w_pos, b_pos, blocks, w_c, b_c, want_x_full=
         x_full = _empty(m, 64, pts) if want_x_full else None
         pool = None if first else _empty(m, 32, pts)
         hr, out = _empty(m, 32, pts), _empty(m, 32, pts)
-        win = None if first else torch.empty(m, 8, dtype=torch.uint8, device=dev)
+        win = None if first else ops.winner_bits(m, 32, dev)
         if last:
             c_out = _empty(m, 32, pts)
         wts = [t.contiguous() for t in (w0, b0, w1, b1, ws)]
@@ -694,9 +670,7 @@ def _trunk_forward_fused(tile, pts, w_pos, b_pos, blocks, w_c, b_c, want_x_full=
             pooled.append(pool)
             winners.append(win)
         net_prev = out
-    if want_x_full:
-        return c_out, nets, pooled, hrs, winners, x_fulls
-    return c_out, nets, pooled, hrs, winners
+    return (c_out, nets, pooled, hrs, winners, x_fulls) if want_x_full else (c_out, nets, pooled, hrs, winners)
 
 
 def _trunk_backward_fused(tile, pts, params, nets, pooled, hrs, winners, g_out):
@@ -705,18 +679,16 @@ def _trunk_backward_fused(tile, pts, params, nets, pooled, hrs, winners, g_out):
     scatter_max -> its arg-max row, pointnet.py:95-98) into its loader, the last block's the backward of
     ``fc_c(relu(.))``, the first block's the fc_pos weight gradient.  Returns the gradients in ``params`` order
     (``None`` where they were accumulated straight into ``param.grad``)."""
-    lib = _lib.load()
-    nb = (len(params) - 4) // 5
-    m = pts.shape[0]
-    w_pos, b_pos, w_c, b_c = params[0], params[1], params[-2], params[-1]
-    direct = _DIRECT_ACCUM and all(p.grad is not None and p.grad.is_contiguous() for p in params)
-    grads = [None] * len(params)
+    w_pos, b_pos, blocks, w_c, b_c = _split_params(params)
+    nb, m = len(blocks), pts.shape[0]
+    direct = _PASS.enabled and all(p.grad is not None and p.grad.is_contiguous() for p in params)
+    dsts = [None] * nb                                   # per block: where its five gradients + fc_pos's / fc_c's two go
     ws_bytes = _lib.ws_bytes("t2h_trunk_block_bwd_workspace_bytes", m)
     ws = _lib.workspace(ws_bytes, pts.device)            # reused by every block: launches are stream ordered
     dx_next = None
     for i in range(nb - 1, -1, -1):
         first, last = i == 0, i == nb - 1
-        w0, b0, w1, b1, wsc = params[2 + 5 * i: 7 + 5 * i]
+        w0, b0, w1, b1, wsc = blocks[i]
         dx = None if first else _empty(m, 64, pts)
         nbytes = m * ((128 if last else 256 + 8 + 4) + 128 + (4 * pts.shape[1] if first else 256) + (128 if last else 0)
                       + (0 if first else 256))
@@ -732,23 +704,17 @@ def _trunk_backward_fused(tile, pts, params, nets, pooled, hrs, winners, g_out):
                   _lib.ptr(wsc.contiguous()), m, None if dx is None else _lib.ptr(dx), _lib.ptr(ws), ws_bytes, _lib.stream(),
                   nbytes=nbytes, flops=flops,
                   tag="t2h_trunk_block_bwd[%s]" % ("first" if first else ("last" if last else "mid")))
-        extra = (w_pos, b_pos) if first else ((w_c, b_c) if last else None)
+        own = (w0, b0, w1, b1, wsc, *((w_pos, b_pos) if first else ((w_c, b_c) if last else (None, None))))
         if direct:
-            dst = [w0.grad, b0.grad, w1.grad, b1.grad, wsc.grad] + ([extra[0].grad, extra[1].grad] if extra else [None, None])
+            dst = [None if t is None else t.grad for t in own]
         else:
-            dst = [torch.empty_like(t, memory_format=torch.contiguous_format) for t in (w0, b0, w1, b1, wsc)]
-            dst += [torch.empty_like(t, memory_format=torch.contiguous_format) for t in extra] if extra else [None, None]
-            grads[2 + 5 * i: 7 + 5 * i] = dst[:5]
-            if first:
-                grads[0], grads[1] = dst[5], dst[6]
-            if last:
-                grads[-2], grads[-1] = dst[5], dst[6]
+            dst = dsts[i] = [None if t is None else torch.empty_like(t, memory_format=torch.contiguous_format) for t in own]
         _lib.call("t2h_trunk_block_reduce", _lib.ptr(ws), m, int(first), int(last), _lib.ptr(dst[0]), _lib.ptr(dst[1]),
                   _lib.ptr(dst[2]), _lib.ptr(dst[3]), _lib.ptr(dst[4]), None if dst[5] is None else _lib.ptr(dst[5]),
                   None if dst[6] is None else _lib.ptr(dst[6]), 1 if direct else 0, _lib.stream(),
                   nbytes=ws_bytes, tag="t2h_trunk_block_reduce")
         dx_next = dx
-    return grads
+    return [None] * len(params) if direct else _join_grads(dsts[0][5:], [d[:5] for d in dsts], dsts[-1][5:])
 
 
 class _PointTrunk(torch.autograd.Function):
@@ -760,35 +726,27 @@ class _PointTrunk(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, tile, pts, pool, *params):
-        n_blocks = (len(params) - 4) // 5
-        ctx.pool = pool
-        w_pos, b_pos = params[0], params[1]
-        blocks = [params[2 + 5 * i: 7 + 5 * i] for i in range(n_blocks)]
-        w_c, b_c = params[-2], params[-1]
-        m = pts.shape[0]
-        h = blocks[0][2].shape[0]
-        ctx.tile, ctx.n_blocks, ctx.h = tile, n_blocks, h
-        if pool == "max" and _fused_trunk_applicable(pts, params, n_blocks):
-            out, nets, pooled, hrs, winners = _trunk_forward_fused(tile, pts, w_pos, b_pos, blocks, w_c, b_c)
-            ctx.fused = True                               # (block 0's input is recomputed from the points in the backward)
-            ctx.save_for_backward(pts, *params, *nets, *pooled[1:], *hrs, *winners)
+        w_pos, b_pos, blocks, w_c, b_c = _split_params(params)
+        n_blocks, m, h = len(blocks), pts.shape[0], blocks[0][2].shape[0]
+        ctx.pool, ctx.tile, ctx.n_blocks, ctx.h = pool, tile, n_blocks, h
+        ctx.fused = pool == "max" and _fused_trunk_applicable(pts, w_pos, blocks, w_c)
+        if ctx.fused:                                      # (block 0's input is recomputed from the points in the backward)
+            out, *kept = _trunk_forward_fused(tile, pts, w_pos, b_pos, blocks, w_c, b_c)
+            ctx.save_for_backward(pts, *params, *_pack_fused(*kept))
             return out
-        ctx.fused = False
         if pts.shape[1] != w_pos.shape[1]:                 # (a ragged TileIndex keeps the tile index in one more column)
             pts = pts[:, :w_pos.shape[1]].contiguous()
-        cats, hrs, winners = [], [], []
-        cat0 = _empty(m, w_pos.shape[0], pts)
-        linear_fwd_(pts, w_pos, b_pos, cat0)                                   # pointnet.py:72
-        cats.append(cat0)
+        cats, hrs, winners = [_empty(m, w_pos.shape[0], pts)], [], []
+        linear_fwd_(pts, w_pos, b_pos, cats[0])                                # pointnet.py:72
         for i, (w0, b0, w1, b1, ws) in enumerate(blocks):
             last = i == n_blocks - 1
             nxt = _empty(m, h, pts) if last else _empty(m, 2 * h, pts)
             hrs.append(_resblock_fwd(cats[i], w0, b0, w1, b1, ws, nxt[:, :h]))     # pointnet.py:73,79
             if not last and pool == "mean":
-                _pool_mean_(tile, nxt[:, :h], nxt[:, h:], accumulate=False)        # pointnet.py:77-78, scatter_mean
+                ops.pool_mean_(tile, nxt[:, :h], nxt[:, h:], accumulate=False)     # pointnet.py:77-78, scatter_mean
             elif not last:
-                win = torch.empty(m, _lib.load().t2h_pool_winner_stride(h), dtype=torch.uint8, device=pts.device)
-                _pool_fwd_(tile, nxt[:, :h], nxt[:, h:], win)                      # pointnet.py:77-78
+                win = ops.winner_bits(m, h, pts.device)
+                ops.pool_max_fwd_(tile, nxt[:, :h], nxt[:, h:], win)               # pointnet.py:77-78
                 winners.append(win)
             cats.append(nxt)
         out = _empty(m, w_c.shape[0], pts)
@@ -799,41 +757,28 @@ class _PointTrunk(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_out):
         nb, h, tile = ctx.n_blocks, ctx.h, ctx.tile
-        saved = ctx.saved_tensors
-        pts = saved[0]
-        n_params = 4 + 5 * nb
-        params = saved[1:1 + n_params]
-        cats = saved[1 + n_params: 2 + n_params + nb]          # nb + 1 buffers
-        hrs = saved[2 + n_params + nb: 2 + n_params + 2 * nb]
-        winners = saved[2 + n_params + 2 * nb:]
-        w_pos, b_pos = params[0], params[1]
-        blocks = [params[2 + 5 * i: 7 + 5 * i] for i in range(nb)]
-        w_c, b_c = params[-2], params[-1]
-
+        pts, *saved = ctx.saved_tensors
+        params, rest = saved[:4 + 5 * nb], saved[4 + 5 * nb:]
         g_out = g_out.contiguous()
         if ctx.fused:
-            rest = saved[1 + n_params:]
-            nets, pooled, hrs, winners = rest[:nb], [None, *rest[nb:2 * nb - 1]], rest[2 * nb - 1:3 * nb - 1], rest[3 * nb - 1:]
-            return (None, None, None, *_trunk_backward_fused(tile, pts, params, nets, pooled, hrs, winners, g_out.contiguous()))
-        dw_c, db_c = _wgrad(g_out, cats[-1], w_c, b_c, relu_in=True)
+            return (None, None, None, *_trunk_backward_fused(tile, pts, params, *_unpack_fused(rest, nb), g_out))
+        w_pos, b_pos, blocks, w_c, b_c = _split_params(params)
+        cats, hrs, winners = rest[:nb + 1], rest[nb + 1: 2 * nb + 1], rest[2 * nb + 1:]
+        g_c = _wgrad(g_out, cats[-1], w_c, b_c, relu_in=True)
         g = linear_dgrad_(g_out, w_c, torch.empty_like(cats[-1]), mask=cats[-1])     # grad of the last block output
-        grads = [None] * n_params
-        grads[-2], grads[-1] = dw_c, db_c
+        g_blocks = [None] * nb
         for i in range(nb - 1, -1, -1):
-            w0, b0, w1, b1, ws = blocks[i]
-            dx, dw0, db0, dw1, db1, dws = _resblock_bwd(g, cats[i], hrs[i], w0, b0, w1, b1, ws)
-            grads[2 + 5 * i: 7 + 5 * i] = [dw0, db0, dw1, db1, dws]
+            dx, *g_blocks[i] = _resblock_bwd(g, cats[i], hrs[i], *blocks[i])
             if i > 0:
                 # dx = [d net | d pooled]: fold the pool's gradient into the left half, which is then d(net_i)
                 if ctx.pool == "mean":
-                    _pool_mean_(tile, dx[:, h:], dx[:, :h], accumulate=True)
+                    ops.pool_mean_(tile, dx[:, h:], dx[:, :h], accumulate=True)
                 else:
-                    _pool_bwd_(tile, dx[:, h:], winners[i - 1], dx[:, :h], accumulate=True)
+                    ops.pool_max_bwd_(tile, dx[:, h:], winners[i - 1], dx[:, :h], accumulate=True)
                 g = dx[:, :h]
             else:
                 g = dx
-        grads[0], grads[1] = _wgrad(g, pts, w_pos, b_pos)
-        return (None, None, None, *grads)
+        return (None, None, None, *_join_grads(_wgrad(g, pts, w_pos, b_pos), g_blocks, g_c))
 
 
 def point_trunk(tile, pts, fc_pos, blocks, fc_c, pool="max") -> torch.Tensor:

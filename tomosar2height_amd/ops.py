@@ -20,6 +20,89 @@ def _f32(t: torch.Tensor, what: str) -> torch.Tensor:
     return t
 
 
+# --------------------------------------------------------------------------------------- raw launchers
+# One in-place launcher per point-side entry point, for the autograd Functions below, the block-by-block trunk of mlp.py and
+# deferred.py: tensors may be column slices ((ptr, ld) from ``_rows``); nbytes / flops / tag are computed here, once.
+def _rows(t: torch.Tensor, what: str):
+    """A 2-D fp32 device view whose rows are contiguous (row stride >= width): returns (ptr, ld)."""
+    if t.dim() != 2 or t.dtype != torch.float32 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise ValueError(f"{what}: expected a 2-D float32 tensor with unit inner stride, got {tuple(t.shape)} "
+                         f"strides {t.stride()}")
+    if not t.is_cuda:
+        raise RuntimeError(f"{what}: expected device tensors; tomosar2height_amd has no CPU path "
+                           "(the CPU restatement lives in oracle/ for tests only)")
+    return t.data_ptr(), (t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1]))
+
+
+def winner_bits(m, c, device):
+    """The arg-max bits of one max pooling over ``m`` rows of ``c`` channels (include/t2h.h, t2h_pool_winner_stride)."""
+    return torch.empty(m, _lib.ws_bytes("t2h_pool_winner_stride", c), dtype=torch.uint8, device=device)
+
+
+def pool_max_fwd_(tile, feat, pooled, winner):
+    (fp, ldf), (pp, ldp) = _rows(feat, "pool feat"), _rows(pooled, "pool out")
+    c = feat.shape[1]
+    # forward: the cell-parallel kernel is the faster one (13 vs 24 us at the bench shape); backward: the row-balanced one
+    _lib.call("t2h_pool_max_fwd", fp, ldf, _lib.ptr(tile.off0), tile.B, tile.nbits, c, pp, ldp, _lib.ptr(winner),
+              _lib.stream(), nbytes=8 * c * tile.n_points + 4 * tile.n_points)
+
+
+def pool_max_bwd_(tile, gpooled, winner, gfeat, accumulate):
+    (gp, ldg), (op, ldo) = _rows(gpooled, "pool gpooled"), _rows(gfeat, "pool gfeat")
+    c = gpooled.shape[1]
+    nbytes = 8 * c * tile.n_points + 4 * tile.n_points
+    # the row-balanced kernels (t2h_pool_rows_*: 14 vs 26 us at the bench shape) serve 16-byte rows of up to 64 channels
+    if c % 4 == 0 and c <= 64 and ldg % 4 == 0 and ldo % 4 == 0:
+        _lib.call("t2h_pool_rows_bwd", gp, ldg, _lib.ptr(winner), _lib.ptr(tile.cell), _lib.ptr(tile.off0), tile.n_points, c,
+                  1 if accumulate else 0, op, ldo, _lib.stream(), nbytes=nbytes, tag="t2h_pool_max_bwd")
+    else:
+        _lib.call("t2h_pool_max_bwd", gp, ldg, _lib.ptr(winner), _lib.ptr(tile.off0), tile.B, tile.nbits, c,
+                  1 if accumulate else 0, op, ldo, _lib.stream(), nbytes=nbytes)
+
+
+def pool_mean_(tile, src, dst, accumulate):
+    """dst (=|+=) per-cell mean of src, scatter_type='mean' (pointnet.py:55-56); its own adjoint, so also the backward."""
+    (sp, lds), (dp, ldd) = _rows(src, "pool src"), _rows(dst, "pool dst")
+    c = src.shape[1]
+    _lib.call("t2h_pool_mean", sp, lds, _lib.ptr(tile.off0), tile.B, tile.nbits, c, 1 if accumulate else 0, dp, ldd,
+              _lib.stream(), nbytes=(8 + (4 if accumulate else 0)) * c * tile.n_points + 4 * tile.n_points)
+
+
+def sample_fwd_(plane_nhwc, pts, dim, b, n, out, tagged=True):
+    """out [rows, C] = the NHWC plane [B, r, r, C] sampled at ``pts`` (row stride ``dim`` floats, ``n`` per batch item)."""
+    r, c, rows = plane_nhwc.shape[1], plane_nhwc.shape[3], out.shape[0]
+    _lib.call("t2h_sample_fwd", _lib.ptr(plane_nhwc), _lib.ptr(pts), dim, b, n, r, c, _lib.ptr(out), _lib.stream(),
+              nbytes=4 * c * rows + 8 * rows + 4 * plane_nhwc.numel(), tag=_lib.timing() and tagged and f"t2h_sample_fwd[C={c},r={r}]")
+
+
+def sample_fwd_relu_(tile, q, r, h, bits=None):
+    """h [N, C] = relu(sample(q)) for the pixel rows ``q`` [B r r, C]; ``bits``: also the packed sign pattern of h."""
+    c = q.shape[1]
+    _lib.call("t2h_sample_fwd_relu", _lib.ptr(q), _lib.ptr(tile.pts), tile.dim, tile.B, tile.N, r, c, _lib.ptr(h),
+              None if bits is None else _lib.ptr(bits), _lib.stream(),
+              nbytes=4 * c * tile.n_points + 8 * tile.n_points + 4 * q.numel() + (c // 8) * tile.n_points * (bits is not None),
+              tag=_lib.timing() and f"t2h_sample_fwd_relu[C={c},r={r}]")
+
+
+def segmean_bwd_(tile, g, level, gfeat, addend=None, add_form=False):
+    """gfeat [N, C] = [addend +] the gradient of the per-cell mean at ``level`` for the NHWC plane gradient ``g``.  ``add_form``:
+    the entry point that takes an addend (which may still be None)."""
+    n, c = gfeat.shape
+    head = (_lib.ptr(g), _lib.ptr(tile.cell), _lib.ptr(tile.off0), tile.B, tile.N, tile.nbits, level, c)
+    nbytes = 4 * g.numel() + 4 * n + 4 * g.numel() // c + 4 * c * n * (2 if addend is not None else 1)
+    tag = _lib.timing() and f"t2h_segmean_bwd[C={c},r={g.shape[1]}]"
+    if add_form:
+        _lib.call("t2h_segmean_bwd_add", *head, None if addend is None else _lib.ptr(addend), _lib.ptr(gfeat), _lib.stream(),
+                  nbytes=nbytes, tag=tag)
+    else:
+        _lib.call("t2h_segmean_bwd", *head, _lib.ptr(gfeat), _lib.stream(), nbytes=nbytes, tag=tag)
+
+
+def nchw_to_nhwc_(src, b, c, p, dst):
+    """dst [B, P, C] = src [B, C, P], both dense (B = 1: a matrix transpose)."""
+    _lib.call("t2h_nchw_to_nhwc", _lib.ptr(src), b, c, p, _lib.ptr(dst), _lib.stream(), nbytes=8 * b * c * p)
+
+
 # --------------------------------------------------------------------------------------- layout glue
 def to_nhwc(x: torch.Tensor) -> torch.Tensor:
     """[B,C,H,W] (any strides) -> contiguous [B,H,W,C]; free when x is already channels_last."""
@@ -30,7 +113,7 @@ def to_nhwc(x: torch.Tensor) -> torch.Tensor:
     _lib.require_device(x, what="to_nhwc")
     b, c, h, w = x.shape
     out = torch.empty(b, h, w, c, dtype=x.dtype, device=x.device)
-    _lib.call("t2h_nchw_to_nhwc", _lib.ptr(x), b, c, h * w, _lib.ptr(out), _lib.stream(), nbytes=8 * x.numel())
+    nchw_to_nhwc_(x, b, c, h * w, out)
     return out
 
 
@@ -57,36 +140,31 @@ def _is_channels_last(x: torch.Tensor) -> bool:
 
 
 # --------------------------------------------------------------------------------------- pool_local
+def _point_rows(feat, tile, what):
+    feat = _f32(feat, what).contiguous()
+    _lib.require_device(feat, what=what)
+    if feat.shape[0] != tile.n_points:
+        raise ValueError(f"{what}: {feat.shape[0]} feature rows for a tile of {tile.n_points} points")
+    return feat
+
+
 class _PoolMax(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feat, tile: TileIndex):
-        feat = _f32(feat, "pool_max").contiguous()
-        _lib.require_device(feat, what="pool_max")
-        n, c = feat.shape
-        if n != tile.n_points:
-            raise ValueError(f"pool_max: {n} feature rows for a tile of {tile.n_points} points")
+        feat = _point_rows(feat, tile, "pool_max")
         pooled = torch.empty_like(feat)
-        winner = torch.empty(n, _lib.load().t2h_pool_winner_stride(c), dtype=torch.uint8, device=feat.device)
-        _lib.call("t2h_pool_max_fwd", _lib.ptr(feat), c, _lib.ptr(tile.off0), tile.B, tile.nbits, c, _lib.ptr(pooled), c,
-                  _lib.ptr(winner), _lib.stream(), nbytes=8 * c * n + 4 * n)
-        ctx.tile, ctx.c = tile, c
+        winner = winner_bits(feat.shape[0], feat.shape[1], feat.device)
+        pool_max_fwd_(tile, feat, pooled, winner)
+        ctx.tile = tile
         ctx.save_for_backward(winner)
         return pooled
 
     @staticmethod
     def backward(ctx, gpooled):
         (winner,) = ctx.saved_tensors
-        tile = ctx.tile
         gpooled = gpooled.contiguous()
         gfeat = torch.empty_like(gpooled)
-        if ctx.c % 4 == 0 and ctx.c <= 64:          # row-balanced backward (14 vs 26 us at the bench shape)
-            _lib.call("t2h_pool_rows_bwd", _lib.ptr(gpooled), ctx.c, _lib.ptr(winner), _lib.ptr(tile.cell), _lib.ptr(tile.off0),
-                      tile.n_points, ctx.c, 0, _lib.ptr(gfeat), ctx.c, _lib.stream(),
-                      nbytes=8 * ctx.c * tile.n_points + 4 * tile.n_points, tag="t2h_pool_max_bwd")
-        else:
-            _lib.call("t2h_pool_max_bwd", _lib.ptr(gpooled), ctx.c, _lib.ptr(winner), _lib.ptr(tile.off0), tile.B,
-                      tile.nbits, ctx.c, 0, _lib.ptr(gfeat), ctx.c, _lib.stream(),
-                      nbytes=8 * ctx.c * tile.n_points + 4 * tile.n_points)
+        pool_max_bwd_(ctx.tile, gpooled, winner, gfeat, accumulate=False)
         return gfeat, None
 
 
@@ -98,24 +176,17 @@ def pool_max(tile: TileIndex, feat: torch.Tensor) -> torch.Tensor:
 class _PoolMean(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feat, tile: TileIndex):
-        feat = _f32(feat, "pool_mean").contiguous()
-        _lib.require_device(feat, what="pool_mean")
-        n, c = feat.shape
-        if n != tile.n_points:
-            raise ValueError(f"pool_mean: {n} feature rows for a tile of {tile.n_points} points")
+        feat = _point_rows(feat, tile, "pool_mean")
         pooled = torch.empty_like(feat)
-        _lib.call("t2h_pool_mean", _lib.ptr(feat), c, _lib.ptr(tile.off0), tile.B, tile.nbits, c, 0, _lib.ptr(pooled), c,
-                  _lib.stream(), nbytes=8 * c * n + 4 * n)
-        ctx.tile, ctx.c = tile, c
+        pool_mean_(tile, feat, pooled, accumulate=False)
+        ctx.tile = tile
         return pooled
 
     @staticmethod
     def backward(ctx, gpooled):
         gpooled = gpooled.contiguous()
-        tile, c = ctx.tile, ctx.c
         gfeat = torch.empty_like(gpooled)
-        _lib.call("t2h_pool_mean", _lib.ptr(gpooled), c, _lib.ptr(tile.off0), tile.B, tile.nbits, c, 0, _lib.ptr(gfeat), c,
-                  _lib.stream(), nbytes=8 * c * tile.n_points + 4 * tile.n_points)
+        pool_mean_(ctx.tile, gpooled, gfeat, accumulate=False)
         return gfeat, None
 
 
@@ -125,14 +196,26 @@ def pool_mean(tile: TileIndex, feat: torch.Tensor) -> torch.Tensor:
 
 
 # --------------------------------------------------------------------------------------- scatter_mean -> plane
+def _rasterise_mean_bwd(ctx, gplane, gthru, add_form):
+    """The backward of both forms: the plain one is the thru form's with no second gradient, on its own entry point."""
+    tile = ctx.tile
+    if gplane is None:
+        return gthru, None, None, None
+    g = to_nhwc(gplane)
+    addend = None
+    if gthru is not None:
+        addend = gthru.contiguous()
+        _lib.require_device(addend, what="rasterise_mean_thru")
+    gfeat = torch.empty(tile.n_points, ctx.c, dtype=torch.float32, device=g.device)
+    segmean_bwd_(tile, g, ctx.level, gfeat, addend, add_form)
+    return gfeat, None, None, None
+
+
 class _RasteriseMean(torch.autograd.Function):
     @staticmethod
     def forward(ctx, feat, tile: TileIndex, level: int, channels_last: bool):
-        feat = _f32(feat, "rasterise_mean").contiguous()
-        _lib.require_device(feat, what="rasterise_mean")
+        feat = _point_rows(feat, tile, "rasterise_mean")
         n, c = feat.shape
-        if n != tile.n_points:
-            raise ValueError(f"rasterise_mean: {n} feature rows for a tile of {tile.n_points} points")
         r = tile.R >> level
         plane = torch.empty(tile.B, r, r, c, dtype=torch.float32, device=feat.device)
         ws_bytes = _lib.ws_bytes("t2h_segmean_workspace_bytes", tile.B, tile.N, tile.nbits, level, c)
@@ -144,14 +227,7 @@ class _RasteriseMean(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gplane):
-        tile = ctx.tile
-        g = to_nhwc(gplane)
-        gfeat = torch.empty(tile.n_points, ctx.c, dtype=torch.float32, device=g.device)
-        _lib.call("t2h_segmean_bwd", _lib.ptr(g), _lib.ptr(tile.cell), _lib.ptr(tile.off0), tile.B, tile.N, tile.nbits,
-                  ctx.level, ctx.c, _lib.ptr(gfeat), _lib.stream(),
-                  nbytes=4 * g.numel() + 4 * tile.n_points + 4 * g.numel() // ctx.c + 4 * ctx.c * tile.n_points,
-                  tag=_lib.timing() and f"t2h_segmean_bwd[C={ctx.c},r={g.shape[1]}]")
-        return gfeat, None, None, None
+        return _rasterise_mean_bwd(ctx, gplane, None, False)
 
 
 class _RasteriseMeanThru(torch.autograd.Function):
@@ -162,26 +238,11 @@ class _RasteriseMeanThru(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, feat, tile: TileIndex, level: int, channels_last: bool):
-        plane = _RasteriseMean.forward(ctx, feat, tile, level, channels_last)
-        return plane, _alias(feat)
+        return _RasteriseMean.forward(ctx, feat, tile, level, channels_last), _alias(feat)
 
     @staticmethod
     def backward(ctx, gplane, gthru):
-        tile = ctx.tile
-        n, c = tile.n_points, ctx.c
-        if gplane is None:
-            return gthru, None, None, None
-        g = to_nhwc(gplane)
-        addend = None
-        if gthru is not None:
-            addend = gthru.contiguous()
-            _lib.require_device(addend, what="rasterise_mean_thru")
-        gfeat = torch.empty(n, c, dtype=torch.float32, device=g.device)
-        _lib.call("t2h_segmean_bwd_add", _lib.ptr(g), _lib.ptr(tile.cell), _lib.ptr(tile.off0), tile.B, tile.N, tile.nbits,
-                  ctx.level, c, None if addend is None else _lib.ptr(addend), _lib.ptr(gfeat), _lib.stream(),
-                  nbytes=4 * g.numel() + 4 * n + 4 * g.numel() // c + 4 * c * n * (2 if addend is not None else 1),
-                  tag=_lib.timing() and f"t2h_segmean_bwd[C={c},r={g.shape[1]}]")
-        return gfeat, None, None, None
+        return _rasterise_mean_bwd(ctx, gplane, gthru, True)
 
 
 def rasterise_mean_thru(tile: TileIndex, feat: torch.Tensor, reso: int, channels_last: bool = False):
@@ -224,6 +285,14 @@ def _sample_bwd(tile, gout, r, c, addend):
     return gplane
 
 
+def _sample_plane_bwd(ctx, gout, gthru):
+    """The backward of both forms: the plain one is the thru form's with no second gradient."""
+    if gout is None:
+        return gthru, None
+    gplane = _sample_bwd(ctx.tile, gout.contiguous(), ctx.r, ctx.c, None if gthru is None else to_nhwc(gthru))
+    return from_nhwc(gplane, ctx.was_cl), None
+
+
 class _SamplePlane(torch.autograd.Function):
     @staticmethod
     def forward(ctx, plane, tile: TileIndex):
@@ -235,17 +304,13 @@ class _SamplePlane(torch.autograd.Function):
         _lib.require_device(p, what="sample_plane")
         b, r, _, c = p.shape
         out = torch.empty(tile.n_points, c, dtype=torch.float32, device=p.device)
-        _lib.call("t2h_sample_fwd", _lib.ptr(p), _lib.ptr(tile.pts), tile.dim, tile.B, tile.N, r, c, _lib.ptr(out),
-                  _lib.stream(), nbytes=4 * c * tile.n_points + 8 * tile.n_points + 4 * p.numel(),
-                  tag=_lib.timing() and f"t2h_sample_fwd[C={c},r={r}]")
+        sample_fwd_(p, tile.pts, tile.dim, tile.B, tile.N, out)
         ctx.tile, ctx.r, ctx.c = tile, r, c
         return out
 
     @staticmethod
     def backward(ctx, gout):
-        tile, r, c = ctx.tile, ctx.r, ctx.c
-        gplane = _sample_bwd(tile, gout.contiguous(), r, c, None)
-        return from_nhwc(gplane, ctx.was_cl), None
+        return _sample_plane_bwd(ctx, gout, None)
 
 
 class _SamplePlaneThru(torch.autograd.Function):
@@ -255,16 +320,11 @@ class _SamplePlaneThru(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, plane, tile: TileIndex):
-        out = _SamplePlane.forward(ctx, plane, tile)
-        return out, _alias(plane)
+        return _SamplePlane.forward(ctx, plane, tile), _alias(plane)
 
     @staticmethod
     def backward(ctx, gout, gthru):
-        tile, r, c = ctx.tile, ctx.r, ctx.c
-        if gout is None:
-            return gthru, None
-        gplane = _sample_bwd(tile, gout.contiguous(), r, c, None if gthru is None else to_nhwc(gthru))
-        return from_nhwc(gplane, ctx.was_cl), None
+        return _sample_plane_bwd(ctx, gout, gthru)
 
 
 def sample_plane_thru(tile: TileIndex, plane: torch.Tensor):
@@ -599,8 +659,7 @@ class _GridSamplePoints(torch.autograd.Function):
         n = xy.shape[1]
         pts = torch.cat([xy[..., :2], torch.zeros_like(xy[..., :1])], dim=2).contiguous()
         out = torch.empty(b * n, c, dtype=torch.float32, device=p.device)
-        _lib.call("t2h_sample_fwd", _lib.ptr(p), _lib.ptr(pts), 3, b, n, r, c, _lib.ptr(out), _lib.stream(),
-                  nbytes=4 * c * b * n + 8 * b * n + 4 * p.numel())
+        sample_fwd_(p, pts, 3, b, n, out, tagged=False)
         ctx.save_for_backward(pts)
         ctx.shape = (b, c, r, n)
         return out.view(b, n, c).permute(0, 2, 1)

@@ -626,10 +626,7 @@ class Trainer:
                 cur.wait_stream(st)
         self._bwd_done = None
         if self.compose_cache is not None and self.compose_cache.pending:    # (error path: drop what was accumulated)
-            for e in self.compose_cache.levels:
-                e["ga"].zero_()
-                e["gconst"].zero_()
-            self.compose_cache.pending = False
+            self.compose_cache.drop_accumulated()
         self.accumulated_loss = 0.0
         self.accumulated_steps = 0
         self.accumulated_loss_dict = {k: 0.0 for k in self.accumulated_loss_dict}
