@@ -10,6 +10,8 @@ from .model import TomoSAR2Height
 from .decoder import decoder_dict
 from .encoder import encoder_dict
 from .tile import TileIndex
+from .evaluator import DSMEvaluator, dilate_mask
 from ._lib import allow_library_fallback, fallback_counts
 
-__all__ = ["TomoSAR2Height", "decoder_dict", "encoder_dict", "TileIndex", "allow_library_fallback", "fallback_counts"]
+__all__ = ["TomoSAR2Height", "decoder_dict", "encoder_dict", "TileIndex", "DSMEvaluator", "dilate_mask",
+           "allow_library_fallback", "fallback_counts"]

@@ -12,6 +12,8 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 OUT = os.path.join(os.path.dirname(HERE), "libt2h_hip.so")
 ARCH = "gfx950"
+_INCLUDE = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include")
+PUBLIC_HEADERS = [os.path.join(_INCLUDE, "t2h.h"), os.path.join(_INCLUDE, "t2h_eval.h")]
 
 
 def sources():
@@ -22,8 +24,7 @@ def _stale():
     if not os.path.exists(OUT):
         return True
     t = os.path.getmtime(OUT)
-    deps = sources() + glob.glob(os.path.join(HERE, "*.h")) + \
-        [os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "t2h.h")]
+    deps = sources() + glob.glob(os.path.join(HERE, "*.h")) + PUBLIC_HEADERS
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -43,8 +44,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     if not force and not _stale():
         return OUT
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    headers = glob.glob(os.path.join(HERE, "*.h")) + \
-        [os.path.join(os.path.dirname(os.path.dirname(HERE)), "include", "t2h.h")]
+    headers = glob.glob(os.path.join(HERE, "*.h")) + PUBLIC_HEADERS
     newest_header = max(os.path.getmtime(h) for h in headers)
     todo, objs = [], []
     for src in sources():
