@@ -11,7 +11,8 @@ from .decoder import decoder_dict
 from .encoder import encoder_dict
 from .tile import TileIndex
 from .evaluator import DSMEvaluator, dilate_mask
+from .instances import BuildingEvaluator, label_components, segment_medians
 from ._lib import allow_library_fallback, fallback_counts
 
 __all__ = ["TomoSAR2Height", "decoder_dict", "encoder_dict", "TileIndex", "DSMEvaluator", "dilate_mask",
-           "allow_library_fallback", "fallback_counts"]
+           "BuildingEvaluator", "label_components", "segment_medians", "allow_library_fallback", "fallback_counts"]
