@@ -16,6 +16,7 @@ import torch
 
 from . import _lib
 from .evaluator import NONZERO, _plane, _predicate
+from .evaluator import load as _load_evaluator
 
 _vp, _i, _i64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t
 
@@ -47,6 +48,7 @@ def load():
     global _typed
     lib = _lib.load()
     if not _typed:
+        _load_evaluator()               # a mask that is not bool / uint8 goes through t2h_eval_predicate (_mask8)
         for name, (res, args) in SIGNATURES.items():
             try:
                 fn = getattr(lib, name)

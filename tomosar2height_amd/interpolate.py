@@ -1,0 +1,198 @@
+"""Interpolation baselines on the device (reference: scripts/interpolate_nearest.py, scripts/interpolate_idw.py; kernels:
+csrc/dsm_interp.hip).
+
+The rows the network is compared against: keep the highest z of every exactly equal (x, y), then rasterise on a regular grid
+by the nearest neighbour or by inverse-distance weighting over the k = 8 nearest.  ``CloudIndex`` does the de-duplication and
+builds a cell index of the cloud; ``nearest_dsm`` / ``idw_dsm`` return a float64 plane that ``DSMEvaluator.eval`` and
+``BuildingEvaluator.eval`` take as it is; ``grid_knn`` gives the neighbour lists themselves.  Row 0 of a raster is ``ymin``
+(the scripts flip nothing), node (j, i) lies at ``(xmin + i * resolution, ymin + j * resolution)``, and the maximum is excluded:
+``nx = ceil((xmax - xmin) / resolution)``.  Ties at equal distance are resolved by (d2, X, Y) ascending -- the k-d tree of the
+reference has no documented order there.  The Delaunay-linear baseline (scripts/interpolate_bilinear.py) is not built.
+
+The entry points are declared in include/t2h_interp.h and typed here (``SIGNATURES``), not in ``_lib.SIGNATURES``.
+"""
+import ctypes
+import math
+
+import torch
+
+from . import _lib
+
+_vp, _i, _i64, _sz, _d = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_double
+
+_GRID = [_vp, _vp, _i, _d, _d, _d, _i, _i, _d, _i, _i]           # unique, cell_offsets, M, xmin, ymin, h, gx, gy, res, ny, nx
+# name -> (restype, argtypes); mirrors include/t2h_interp.h one to one
+SIGNATURES = {
+    "t2h_interp_max_cells": (_i64, [_i64]),
+    "t2h_interp_bounds_workspace_bytes": (_sz, [_i64]),
+    "t2h_interp_bounds": (_i, [_vp, _i64, _vp, _vp, _sz, _vp]),
+    "t2h_interp_index_workspace_bytes": (_sz, [_i64]),
+    "t2h_interp_index": (_i, [_vp, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "t2h_interp_knn": (_i, _GRID + [_i, _vp, _vp, _vp]),
+    "t2h_interp_nearest": (_i, _GRID + [_vp, _vp]),
+    "t2h_interp_idw": (_i, _GRID + [_i, _vp, _vp]),
+}
+
+TILE = 16               # T2H_INTERP_TILE: nodes per tile edge, one workgroup per tile
+CHUNK = 2048            # T2H_INTERP_CHUNK: points staged in LDS at a time
+MAX_K = 8               # T2H_INTERP_MAX_K
+CELL_POINTS = 4         # T2H_INTERP_CELL_POINTS: input points per cell the cell edge aims at
+TABLE_COLS = 16         # T2H_INTERP_TABLE_COLS
+# bounds: partial rows, final row + cell grid.  index: clear, counts, 3 for the offsets, fill, rank, flags, 3 for their scan,
+# compaction, cell offsets of the unique cloud
+LAUNCHES_PER_BOUNDS = 2
+LAUNCHES_PER_INDEX = 1 + 1 + 3 + 1 + 1 + 1 + 3 + 1 + 1
+LAUNCHES_PER_RASTER = 1
+
+_typed = False
+
+
+def load():
+    """The library handle with the t2h_interp_* entries typed (untyped ctypes calls would truncate 64-bit pointers)."""
+    global _typed
+    lib = _lib.load()
+    if not _typed:
+        for name, (res, args) in SIGNATURES.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError as e:
+                raise _lib.T2HLibraryError(f"{_lib.LIB_PATH} does not export {name}; rebuild it") from e
+            fn.restype, fn.argtypes = res, args
+        _typed = True
+    return lib
+
+
+class CloudIndex:
+    """Bounds, z-max de-duplication and cell index of an [N, 3] cloud of (X, Y, Z).
+
+    ``unique`` [M, 3] float64: one row per distinct (X, Y) with the largest Z, in cell-major order (inside a cell by X, then
+    Y); ``origin`` = (xmin, ymin); ``bounds`` = (xmin, xmax, ymin, ymax); ``grid_shape(resolution)`` = (ny, nx).  Building it
+    costs one 128-byte copy to the host (and the wait for it): the raster's shape depends on what it carries."""
+
+    def __init__(self, points: torch.Tensor):
+        load()
+        if not isinstance(points, torch.Tensor):
+            raise TypeError(f"CloudIndex: expected a torch tensor, got {type(points).__name__}")
+        if points.dtype not in (torch.float32, torch.float64):
+            raise TypeError(f"CloudIndex: points must be float64 (or float32, widened exactly), got {points.dtype}")
+        if points.dim() != 2 or points.shape[1] != 3 or points.shape[0] < 1:
+            raise ValueError(f"CloudIndex: expected [N, 3] points with N >= 1, got {tuple(points.shape)}")
+        if not points.is_cuda:
+            _lib.require_device(points, what="CloudIndex")
+        pts = points.to(torch.float64).contiguous()
+        N, dev = pts.shape[0], pts.device
+        cap = int(load().t2h_interp_max_cells(N))
+        if cap == 0:
+            raise ValueError(f"CloudIndex: {N} points (1 .. 2^31 - 1)")
+        table = torch.empty(TABLE_COLS, dtype=torch.float64, device=dev)
+        unique = torch.empty((N, 3), dtype=torch.float64, device=dev)
+        cell_offsets = torch.empty(cap + 1, dtype=torch.int32, device=dev)
+        st = _lib.stream()
+        need = _lib.ws_bytes("t2h_interp_bounds_workspace_bytes", N)
+        ws = _lib.workspace(need, dev)
+        _lib.call("t2h_interp_bounds", _lib.ptr(pts), N, _lib.ptr(table), _lib.ptr(ws), need, st, nbytes=24 * N)
+        need = _lib.ws_bytes("t2h_interp_index_workspace_bytes", N)
+        ws = _lib.workspace(need, dev)
+        _lib.call("t2h_interp_index", _lib.ptr(pts), N, _lib.ptr(table), _lib.ptr(unique), _lib.ptr(cell_offsets), _lib.ptr(ws),
+                  need, st, nbytes=N * (2 * 24 + 4 * 24 + 24 + 5 * 4) + 5 * 4 * cap)
+        xmin, xmax, ymin, ymax, bad, h, gx, gy, M = table.cpu().tolist()[:9]      # the one copy (and wait)
+        if bad > 0:
+            raise ValueError(f"CloudIndex: {int(bad)} of {N} points have a non-finite coordinate or height (the reference's "
+                             "pandas group-by would skip NaN keys; that is not reproduced)")
+        self.n_points, self.n_unique = N, int(M)
+        self.bounds = (xmin, xmax, ymin, ymax)
+        self.origin = (xmin, ymin)
+        self.cell_edge, self.cells = h, (int(gy), int(gx))
+        self.unique = unique[:self.n_unique]
+        self.cell_offsets = cell_offsets
+        self.device = dev
+
+    def grid_shape(self, resolution: float = 1.0):
+        """``(ny, nx)`` of the raster at ``resolution``: numpy's ``len(arange(min, max, resolution))`` per axis."""
+        res = _resolution(resolution)
+        xmin, xmax, ymin, ymax = self.bounds
+        return (int(math.ceil((ymax - ymin) / res)), int(math.ceil((xmax - xmin) / res)))
+
+    def _grid_args(self, res, ny, nx):
+        return (_lib.ptr(self.unique), _lib.ptr(self.cell_offsets), self.n_unique, self.origin[0], self.origin[1], self.cell_edge,
+                self.cells[1], self.cells[0], res, ny, nx)
+
+
+def _resolution(resolution):
+    res = float(resolution)
+    if not (res > 0.0 and math.isfinite(res)):
+        raise ValueError(f"resolution = {resolution!r}; a positive finite pixel size")
+    return res
+
+
+def _index(points_or_index):
+    return points_or_index if isinstance(points_or_index, CloudIndex) else CloudIndex(points_or_index)
+
+
+def _check_k(index, k, what):
+    if int(k) != k or not 1 <= k <= MAX_K:
+        raise ValueError(f"{what}: k = {k!r} (1 .. {MAX_K})")
+    if index.n_unique < k:
+        raise ValueError(f"{what}: {index.n_unique} distinct (x, y) for k = {k} neighbours (the reference would index past "
+                         "the end of the cloud there)")
+    return int(k)
+
+
+def _work(index, ny, nx):
+    """Algorithmic bytes of one raster launch, for a KernelTimeline: the unique cloud once per tile ring is not known before
+    the run; the floor is the cloud and the offsets once."""
+    return 24 * index.n_unique + 4 * (index.cells[0] * index.cells[1] + 1)
+
+
+def grid_knn(index: CloudIndex, resolution: float = 1.0, k: int = 8):
+    """``(d2 [ny, nx, k] float64, idx [ny, nx, k] int32)``: squared distances and rows of ``index.unique`` of the k nearest
+    neighbours of every raster node, in (d2, X, Y) order."""
+    load()
+    if not isinstance(index, CloudIndex):
+        raise TypeError(f"grid_knn: expected a CloudIndex, got {type(index).__name__}")
+    k = _check_k(index, k, "grid_knn")
+    res = _resolution(resolution)
+    ny, nx = index.grid_shape(res)
+    d2 = torch.empty((ny, nx, k), dtype=torch.float64, device=index.device)
+    idx = torch.empty((ny, nx, k), dtype=torch.int32, device=index.device)
+    if ny * nx > 0:
+        _lib.call("t2h_interp_knn", *index._grid_args(res, ny, nx), k, _lib.ptr(d2), _lib.ptr(idx), _lib.stream(),
+                  nbytes=_work(index, ny, nx) + 12 * k * ny * nx)
+    return d2, idx
+
+
+def nearest_dsm(points_or_index, resolution: float = 1.0):
+    """``(dsm [ny, nx] float64, (xmin, ymin))``: scripts/interpolate_nearest.py on the device."""
+    load()
+    index = _index(points_or_index)
+    _check_k(index, 1, "nearest_dsm")
+    res = _resolution(resolution)
+    ny, nx = index.grid_shape(res)
+    out = torch.empty((ny, nx), dtype=torch.float64, device=index.device)
+    if ny * nx > 0:
+        _lib.call("t2h_interp_nearest", *index._grid_args(res, ny, nx), _lib.ptr(out), _lib.stream(),
+                  nbytes=_work(index, ny, nx) + 16 * ny * nx)
+    return out, index.origin
+
+
+def idw_dsm(points_or_index, resolution: float = 1.0, k: int = 8, power: float = 2):
+    """``(dsm [ny, nx] float64, (xmin, ymin))``: scripts/interpolate_idw.py on the device.  A coincident point has weight 1
+    beside the others' 1 / d^2, as there."""
+    load()
+    if power != 2:
+        raise ValueError(f"idw_dsm: power = {power!r}; only the reference's power = 2 is built")
+    index = _index(points_or_index)
+    k = _check_k(index, k, "idw_dsm")
+    res = _resolution(resolution)
+    ny, nx = index.grid_shape(res)
+    out = torch.empty((ny, nx), dtype=torch.float64, device=index.device)
+    if ny * nx > 0:
+        _lib.call("t2h_interp_idw", *index._grid_args(res, ny, nx), k, _lib.ptr(out), _lib.stream(),
+                  nbytes=_work(index, ny, nx) + (8 + 8 * k) * ny * nx)
+    return out, index.origin
+
+
+def linear_dsm(points_or_index, resolution: float = 1.0):
+    """The Delaunay-linear baseline of scripts/interpolate_bilinear.py is not built."""
+    raise NotImplementedError("linear_dsm: the Delaunay-linear griddata of scripts/interpolate_bilinear.py needs a device "
+                              "triangulation, which is out of scope (DESIGN.md section 7)")
