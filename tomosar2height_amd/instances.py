@@ -4,8 +4,8 @@
 different nonzero values; a footprint mask has one, so here every nonzero pixel is foreground).  ``BuildingEvaluator.eval``
 takes the tensor ``DSMGenerator.generate_dsm()`` returns and gives the reference's RMSE-B / MAE-B / MedAE-B: the median height
 of every building in the prediction and in the ground truth, then the error over the buildings.  The point-cloud variants of
-the same script (evaluator_instance.py:139-291) are not built; ``segment_medians`` takes any plane of values with a plane of
-labels, which is all they would need.
+the same script (evaluator_instance.py:139-291) are ``cloud_instances.py``; ``segment_medians`` takes any plane of values with a
+plane of labels, and gives them their DTM and nDSM medians.
 
 The entry points are declared in include/t2h_inst.h and typed here (``SIGNATURES``), not in ``_lib.SIGNATURES``.
 """
