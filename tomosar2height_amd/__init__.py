@@ -13,10 +13,10 @@ from .tile import TileIndex
 from .evaluator import DSMEvaluator, dilate_mask
 from .instances import BuildingEvaluator, label_components, segment_medians
 from .cloud_instances import CloudBuildingEvaluator, assign_points, point_medians
-from .interpolate import CloudIndex, grid_knn, idw_dsm, linear_dsm, nearest_dsm
+from .interpolate import CloudIndex, delaunay_dsm, grid_knn, grid_simplex, idw_dsm, linear_dsm, nearest_dsm
 from ._lib import allow_library_fallback, fallback_counts
 
 __all__ = ["TomoSAR2Height", "decoder_dict", "encoder_dict", "TileIndex", "DSMEvaluator", "dilate_mask",
            "BuildingEvaluator", "label_components", "segment_medians", "CloudBuildingEvaluator", "assign_points",
            "point_medians", "CloudIndex", "grid_knn", "nearest_dsm", "idw_dsm",
-           "linear_dsm", "allow_library_fallback", "fallback_counts"]
+           "linear_dsm", "delaunay_dsm", "grid_simplex", "allow_library_fallback", "fallback_counts"]

@@ -1,5 +1,5 @@
-"""Interpolation baselines on the device (reference: scripts/interpolate_nearest.py, scripts/interpolate_idw.py; kernels:
-csrc/dsm_interp.hip).
+"""Interpolation baselines on the device (reference: scripts/interpolate_nearest.py, scripts/interpolate_idw.py,
+scripts/interpolate_bilinear.py; kernels: csrc/dsm_interp.hip, csrc/dsm_tin.hip).
 
 The rows the network is compared against: keep the highest z of every exactly equal (x, y), then rasterise on a regular grid
 by the nearest neighbour or by inverse-distance weighting over the k = 8 nearest.  ``CloudIndex`` does the de-duplication and
@@ -7,12 +7,21 @@ builds a cell index of the cloud; ``nearest_dsm`` / ``idw_dsm`` return a float64
 ``BuildingEvaluator.eval`` take as it is; ``grid_knn`` gives the neighbour lists themselves.  Row 0 of a raster is ``ymin``
 (the scripts flip nothing), node (j, i) lies at ``(xmin + i * resolution, ymin + j * resolution)``, and the maximum is excluded:
 ``nx = ceil((xmax - xmin) / resolution)``.  Ties at equal distance are resolved by (d2, X, Y) ascending -- the k-d tree of the
-reference has no documented order there.  The Delaunay-linear baseline (scripts/interpolate_bilinear.py) is not built.
+reference has no documented order there.
 
-The entry points are declared in include/t2h_interp.h and typed here (``SIGNATURES``), not in ``_lib.SIGNATURES``.
+``delaunay_dsm`` is the Delaunay-linear baseline: ``griddata(method='linear')`` of scripts/interpolate_bilinear.py over the
+unique cloud SHIFTED to its (xmin, ymin), NaN outside the convex hull; ``grid_simplex`` gives every node's triangle and
+barycentric coordinates.  No triangulation is built: a node's triangle is found by a local search over the cell index
+(DESIGN.md section 4.8).  On raw world coordinates the script itself interpolates over a triangulation of a SUBSET of the cloud
+(Qhull drops the points its lifted paraboloid cannot resolve); that is not reproduced, and is why ``linear_dsm`` -- the name
+for the script's own output -- stays unbuilt.
+
+The entry points are declared in include/t2h_interp.h and include/t2h_tin.h and typed here (``SIGNATURES``,
+``TIN_SIGNATURES``), not in ``_lib.SIGNATURES``.
 """
 import ctypes
 import math
+import warnings
 
 import torch
 
@@ -33,6 +42,14 @@ SIGNATURES = {
     "t2h_interp_idw": (_i, _GRID + [_i, _vp, _vp]),
 }
 
+# name -> (restype, argtypes); mirrors include/t2h_tin.h one to one
+TIN_SIGNATURES = {
+    "t2h_tin_hull_workspace_bytes": (_sz, [_i64]),
+    "t2h_tin_hull": (_i, [_vp, _i, _d, _d, _vp, _vp, _vp, _sz, _vp]),       # unique, M, xmin, ymin, hull, status, ws, bytes, stream
+    "t2h_tin_simplex": (_i, _GRID + [_vp, _i, _vp, _vp, _vp, _vp]),         # ..., hull, n_hull, tri, bary, status, stream
+    "t2h_tin_linear": (_i, _GRID + [_vp, _i, _vp, _vp, _vp]),               # ..., hull, n_hull, out, status, stream
+}
+
 TILE = 16               # T2H_INTERP_TILE: nodes per tile edge, one workgroup per tile
 CHUNK = 2048            # T2H_INTERP_CHUNK: points staged in LDS at a time
 MAX_K = 8               # T2H_INTERP_MAX_K
@@ -43,16 +60,21 @@ TABLE_COLS = 16         # T2H_INTERP_TABLE_COLS
 LAUNCHES_PER_BOUNDS = 2
 LAUNCHES_PER_INDEX = 1 + 1 + 3 + 1 + 1 + 1 + 3 + 1 + 1
 LAUNCHES_PER_RASTER = 1
+TIN_DIRECTIONS = 16     # T2H_TIN_DIRECTIONS
+TIN_MAX_PIVOTS = 64     # T2H_TIN_MAX_PIVOTS
+TIN_STATUS_COLS = 8     # T2H_TIN_STATUS_COLS
+LAUNCHES_PER_HULL = 4                   # partial extremes, polygon, filter, sort + chain
+LAUNCHES_PER_TIN_RASTER = 1 + 1         # the clear of the status, the search
 
 _typed = False
 
 
 def load():
-    """The library handle with the t2h_interp_* entries typed (untyped ctypes calls would truncate 64-bit pointers)."""
+    """The library handle with the t2h_interp_* and t2h_tin_* entries typed (untyped ctypes calls would truncate 64-bit pointers)."""
     global _typed
     lib = _lib.load()
     if not _typed:
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in {**SIGNATURES, **TIN_SIGNATURES}.items():
             try:
                 fn = getattr(lib, name)
             except AttributeError as e:
@@ -112,6 +134,27 @@ class CloudIndex:
         res = _resolution(resolution)
         xmin, xmax, ymin, ymax = self.bounds
         return (int(math.ceil((ymax - ymin) / res)), int(math.ceil((xmax - xmin) / res)))
+
+    def hull(self):
+        """``hull [n] int32``: the convex hull of ``unique`` as rows of it, counter-clockwise from the smallest (X, Y), points on
+        an edge left out.  Computed once and kept (one 32-byte copy to the host, and the wait for it).  ``ValueError`` for a
+        cloud with fewer than 3 distinct points or with all of them on one line."""
+        hit = getattr(self, "_hull", None)
+        if hit is None:
+            M, dev = self.n_unique, self.device
+            hull = torch.empty(M + 1, dtype=torch.int32, device=dev)
+            status = torch.empty(TIN_STATUS_COLS, dtype=torch.int32, device=dev)
+            need = _lib.ws_bytes("t2h_tin_hull_workspace_bytes", M)
+            ws = _lib.workspace(need, dev)
+            _lib.call("t2h_tin_hull", _lib.ptr(self.unique), M, self.origin[0], self.origin[1], _lib.ptr(hull), _lib.ptr(status),
+                      _lib.ptr(ws), need, _lib.stream(), nbytes=2 * 24 * M)
+            n, degenerate, survivors = status.cpu().tolist()[:3]                  # the one copy (and wait)
+            self.hull_survivors = survivors
+            hit = self._hull = (None if degenerate else hull[:n],)
+        if hit[0] is None:
+            raise ValueError(f"CloudIndex.hull: the {self.n_unique} distinct (x, y) of this cloud span no area (fewer than 3, or all "
+                             "on one line): there is no triangle to interpolate over (Qhull refuses such input too)")
+        return hit[0]
 
     def _grid_args(self, res, ny, nx):
         return (_lib.ptr(self.unique), _lib.ptr(self.cell_offsets), self.n_unique, self.origin[0], self.origin[1], self.cell_edge,
@@ -192,7 +235,60 @@ def idw_dsm(points_or_index, resolution: float = 1.0, k: int = 8, power: float =
     return out, index.origin
 
 
+def _tin_status(status, what, return_status):
+    capped, unresolved, pivots, walk_pivots = status.cpu().tolist()[:4]           # one 32-byte copy (and wait)
+    out = {"capped": capped, "unresolved": unresolved, "pivots": pivots, "walk_pivots": walk_pivots}
+    if (capped or unresolved) and not return_status:
+        warnings.warn(f"{what}: {capped} nodes stopped at {TIN_MAX_PIVOTS} pivots and {unresolved} nodes inside the hull found no "
+                      "triangle; their values are not the Delaunay interpolant (pass return_status=True for the counts)",
+                      RuntimeWarning, stacklevel=3)
+    return out
+
+
+def grid_simplex(index: CloudIndex, resolution: float = 1.0, return_status: bool = False):
+    """``(tri [ny, nx, 3] int32, bary [ny, nx, 3] float64)``: for every raster node the Delaunay triangle of the shifted unique
+    cloud that contains it, as rows of ``index.unique`` in ascending order, and its barycentric coordinates in that order;
+    -1 / NaN outside the convex hull.  The counterpart of ``grid_knn``.  With ``return_status`` a third value: ``{"capped":
+    nodes that stopped at 64 pivots, "unresolved": ..., "pivots": ..., "walk_pivots": ...}``; without it, nodes that were capped
+    raise a ``RuntimeWarning``."""
+    load()
+    if not isinstance(index, CloudIndex):
+        raise TypeError(f"grid_simplex: expected a CloudIndex, got {type(index).__name__}")
+    res = _resolution(resolution)
+    hull = index.hull()
+    ny, nx = index.grid_shape(res)
+    tri = torch.empty((ny, nx, 3), dtype=torch.int32, device=index.device)
+    bary = torch.empty((ny, nx, 3), dtype=torch.float64, device=index.device)
+    status = torch.zeros(TIN_STATUS_COLS, dtype=torch.int32, device=index.device)
+    if ny * nx > 0:
+        _lib.call("t2h_tin_simplex", *index._grid_args(res, ny, nx), _lib.ptr(hull), hull.shape[0], _lib.ptr(tri), _lib.ptr(bary),
+                  _lib.ptr(status), _lib.stream(), nbytes=_work(index, ny, nx) + 36 * ny * nx)
+    st = _tin_status(status, "grid_simplex", return_status)
+    return (tri, bary, st) if return_status else (tri, bary)
+
+
+def delaunay_dsm(points_or_index, resolution: float = 1.0, return_status: bool = False):
+    """``(dsm [ny, nx] float64, (xmin, ymin))``: scripts/interpolate_bilinear.py on the device, over the unique cloud shifted to
+    its (xmin, ymin) -- ``griddata(method='linear')`` there -- NaN outside the convex hull.  On raw world coordinates the
+    script's Qhull drops points, which is not reproduced.  A cloud without area raises ``ValueError``.
+    ``return_status`` as for ``grid_simplex``."""
+    load()
+    index = _index(points_or_index)
+    res = _resolution(resolution)
+    hull = index.hull()
+    ny, nx = index.grid_shape(res)
+    out = torch.empty((ny, nx), dtype=torch.float64, device=index.device)
+    status = torch.zeros(TIN_STATUS_COLS, dtype=torch.int32, device=index.device)
+    if ny * nx > 0:
+        _lib.call("t2h_tin_linear", *index._grid_args(res, ny, nx), _lib.ptr(hull), hull.shape[0], _lib.ptr(out), _lib.ptr(status),
+                  _lib.stream(), nbytes=_work(index, ny, nx) + 8 * ny * nx)
+    st = _tin_status(status, "delaunay_dsm", return_status)
+    return (out, index.origin, st) if return_status else (out, index.origin)
+
+
 def linear_dsm(points_or_index, resolution: float = 1.0):
-    """The Delaunay-linear baseline of scripts/interpolate_bilinear.py is not built."""
-    raise NotImplementedError("linear_dsm: the Delaunay-linear griddata of scripts/interpolate_bilinear.py needs a device "
-                              "triangulation, which is out of scope (DESIGN.md section 7)")
+    """The output of scripts/interpolate_bilinear.py on raw world coordinates is not built; the baseline
+    itself is ``delaunay_dsm``."""
+    raise NotImplementedError("linear_dsm: the output of scripts/interpolate_bilinear.py on raw world coordinates, with the points "
+                              "Qhull drops there, is not reproduced; use delaunay_dsm, the same griddata on the cloud shifted "
+                              "to its origin (DESIGN.md section 7)")
