@@ -1,0 +1,70 @@
+/* t2h_pnpp.h -- C ABI of the PointNet++ point stages in libt2h_hip.so (csrc/pnpp.hip): farthest point sampling, radius
+ * grouping, grouped rows, grouped max and 3-nearest-neighbour feature propagation -- the index and gather work of the
+ * reference's tomosar2height/encoder/pointnetpp.py (farthest_point_sample :220-241, query_ball_point :244-264,
+ * sample_and_group :279-296, torch.max(new_points, 2) :55, PointNetFeaturePropagation.forward :90-97).  Forward only: the
+ * encoder built on them runs in eval().
+ *
+ * Same conventions as t2h.h: device pointers owned by the caller, no allocation, no state, stream-ordered calls, 0 or a
+ * negative T2H_ERR_* code, every argument validated before any launch.  The entries live in the same library but are typed by
+ * tomosar2height_amd/pointops.py (its own SIGNATURES table); T2H_ABI_VERSION is unchanged.
+ *
+ * Inputs are dense [B, N, ...] fp32.  Every squared distance is taken by differences,
+ *   d2 = ((dx * dx + dy * dy) + dz * dz),  dx = x - cx, ...   each operation rounded once in fp32, no fused multiply-add,
+ * never by the reference's -2 x.y + |x|^2 + |y|^2 matmul form, whose rounding depends on the BLAS underneath.  No kernel
+ * uses a float atomic, waits for another workgroup or depends on scheduling: two runs give the same bytes.
+ */
+#ifndef T2H_PNPP_H_
+#define T2H_PNPP_H_
+
+#include "t2h.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#define T2H_FPS_ONE_WG_MAX 2048   /* largest N of the one-workgroup form (16 bytes of LDS per point: 32 KB) */
+
+/* Bytes t2h_fps needs for (B, N) at `slice` points per workgroup (0: the one-workgroup form, which needs none; 1 byte is
+ * reported so that the caller always has a buffer).  0 for arguments the entry would refuse. */
+size_t t2h_fps_workspace_bytes(int B, int N, int slice);
+
+/* Farthest point sampling: centroids [B, npoint] int64.  centroids[b, 0] = start[b] (int64 [B], clamped to [0, N)); then
+ * `npoint - 1` times: distance[i] = min(distance[i], d2(i, last centroid)) (the reference's `dist < distance` update, from
+ * 1e10), next centroid = the LOWEST index at which distance is largest.  That tie rule is this library's: the reference takes
+ * whatever torch.max returns among equal maxima.  N < npoint repeats centroids as the reference does (all distances 0 ->
+ * index 0).
+ * slice == 0: one workgroup per cloud, coordinates and distances in LDS, N <= T2H_FPS_ONE_WG_MAX.
+ * slice  > 0 (a multiple of 64): one LAUNCH per centroid over ceil(N / slice) workgroups per cloud.  Each workgroup first
+ *   reduces the previous launch's per-slice (max, index) partials to find the centroid, then updates its own slice of the
+ *   distances and writes its partial into the other half of a ping-pong pair.  Launch boundaries are the only
+ *   synchronisation.  Both forms give the same bytes. */
+int t2h_fps(const float *xyz, int B, int N, int npoint, const int64_t *start, int slice, int64_t *centroids, void *workspace,
+            size_t workspace_bytes, t2h_stream_t stream);
+
+/* Radius grouping: idx [B, S, nsample] int64 = per query new_xyz[b, s] the first `nsample` indices i, in index order, with
+ * NOT (d2(xyz[b, i], query) > radius2); the remaining slots repeat the first index found.  A query that is one of the points
+ * is always inside its own ball, so a group is never empty for the encoder; if it ever is, every slot holds N as in the
+ * reference.  One wave per query, scanning 64 points at a time, leaving as soon as `nsample` are found. */
+int t2h_ball_query(const float *xyz, const float *new_xyz, int B, int N, int S, float radius2, int nsample, int64_t *idx,
+                   t2h_stream_t stream);
+
+/* Grouped rows for the layers' products: rows [B * S * nsample, ld] fp32, row (b, s, j) =
+ *   xyz[b, idx[b, s, j]] - new_xyz[b, s]  (3 columns) | points[b, idx[b, s, j]]  (D columns; points may be NULL with D = 0)
+ *   | zeros up to ld >= 3 + D.   An index outside [0, N) (the empty group above) reads row N - 1. */
+int t2h_group_rows(const float *xyz, const float *new_xyz, const float *points, const int64_t *idx, int B, int N, int S,
+                   int nsample, int D, int ld, float *rows, t2h_stream_t stream);
+
+/* out [groups, C] = max over the `nsample` consecutive rows of each group of rows [groups * nsample, ld] (columns 0 .. C). */
+int t2h_group_max(const float *rows, int ld, int64_t groups, int nsample, int C, float *out, t2h_stream_t stream);
+
+/* 3-nearest-neighbour feature propagation from S sources (xyz2 [B, S, 3], points2 [B, S, D]) to N targets (xyz1 [B, N, 3]):
+ * idx [B, N, 3] int64 = the three smallest d2 in ascending order, equal d2 in ascending index; r_k = 1 / (d2_k + 1e-8),
+ * weight [B, N, 3] = r_k / ((r_0 + r_1) + r_2), out [B, N, D] = (p_0 * w_0 + p_1 * w_1) + p_2 * w_2.  S == 1 is the reference's
+ * `repeat` branch: idx 0, weight (1, 0, 0), out = the one source row (any D >= 1).  S == 2 is refused, as the reference fails on it. */
+int t2h_three_nn_interp(const float *xyz1, const float *xyz2, const float *points2, int B, int N, int S, int D, int64_t *idx,
+                        float *weight, float *out, t2h_stream_t stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* T2H_PNPP_H_ */

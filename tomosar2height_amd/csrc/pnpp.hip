@@ -1,0 +1,379 @@
+// PointNet++ point stages on the device (reference: tomosar2height/encoder/pointnetpp.py; ABI in include/t2h_pnpp.h):
+// farthest point sampling, radius grouping, grouped rows, grouped max, 3-nearest-neighbour feature propagation.  Forward only.
+//
+// FPS: the running distance of every point to the chosen set and, per centroid, an arg-max with the lowest index among equal
+//   maxima.  Distances are sums of squares, so never negative and never NaN after the min: their bit patterns order as unsigned
+//   integers.  The arg-max is two integer reductions -- the maximum of the bits, then the minimum of
+//   (index | 0x7fffffff where the bits differ from the maximum) -- v_max_u32 / v_min_u32, no compare.
+//   One-workgroup form: coordinates and distances of a cloud in LDS (16 B per point), one barrier per reduction, two per centroid.
+//   Sliced form: one launch per centroid; every workgroup repeats the (cheap) reduction of the previous launch's per-slice
+//   partials, updates its slice and leaves its own partial in the other half of a ping-pong pair.  No workgroup ever waits for
+//   another one: launch boundaries order everything.
+//
+// BALL QUERY: one wave per query walks the cloud 64 points at a time; the in-ball lanes of a step are a ballot (a scalar
+//   mask), their output slots the running count plus the population of the lower lanes' bits.
+//
+// THREE-NN: one target per thread, sources staged through LDS 512 at a time, a sorted list of three (d2, index) in registers;
+//   a source replaces an entry only when strictly closer, and sources arrive in index order, so equal d2 keep the lower index.
+//
+// Compare results and vector selects (audited on the emitted assembly with isa_pass.lifetimes, figures in
+//   DESIGN.md section 4.9).  These kernels run in the same forward as the split convolutions of the U-Net, on the same stream,
+//   and could share a CU with those of another stream.  fps_one, group_rows, nn_interp and nn_repeat contain no v_cndmask:
+//   lanes are exchanged with ds_bpermute (__shfl_xor carries a bounds select), the arg-max factor comes from an opaque
+//   v_min_u32, grids are per group so that no flat index is divided.  fps_slice and group_max keep one v_cndmask 0, 1 from a
+//   scalar-written mask; the ball query's ballot is read by v_mbcnt as data and its store re-compares in a branch.
+//   three_nn_kernel is NOT select-free: its sorted insertion is 20 v_cndmask, each fed by a compare at most 6 instructions
+//   earlier.
+#include <math.h>
+
+#include "t2h_common.h"
+#include "../../include/t2h_pnpp.h"
+
+namespace t2h {
+
+constexpr int kFpsOneThreads = 512;
+constexpr int kFpsSliceThreads = 256;
+constexpr int kNnThreads = 256;
+constexpr int kNnChunk = 512;
+
+__device__ inline float pn_d2(float x, float y, float z, float cx, float cy, float cz) {
+    const float dx = __fsub_rn(x, cx), dy = __fsub_rn(y, cy), dz = __fsub_rn(z, cz);
+    return __fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz));
+}
+
+// index where the bits equal the maximum, 0x7fffffff elsewhere: no compare (bits <= maxbits always).  The clamp is an opaque
+// v_min_u32: written as min(x, 1u) the compiler recognises the idiom and emits the very v_cmp_eq + v_cndmask this avoids.
+__device__ inline unsigned pn_candidate(unsigned maxbits, unsigned bits, unsigned index) {
+    unsigned differs;
+    asm("v_min_u32 %0, %1, 1" : "=v"(differs) : "v"(maxbits - bits));
+    return index | ((0u - differs) >> 1);
+}
+// max without the NaN test hipcc wraps around fmaxf (a v_cmp_u + v_cndmask per element)
+__device__ inline float pn_max(float a, float b) {
+    float m;
+    asm("v_max_f32 %0, %1, %2" : "=v"(m) : "v"(a), "v"(b));
+    return m;
+}
+
+// lane ^ o through ds_bpermute: unlike __shfl_xor it carries no bounds select (every partner lane exists in a full wave)
+__device__ inline unsigned pn_xor_lane(unsigned v, int o) {
+    return (unsigned)__builtin_amdgcn_ds_bpermute((int)(((threadIdx.x & 63) ^ o) << 2), (int)v);
+}
+__device__ inline unsigned pn_wave_max(unsigned v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = max(v, pn_xor_lane(v, o));
+    return v;
+}
+__device__ inline unsigned pn_wave_min(unsigned v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, pn_xor_lane(v, o));
+    return v;
+}
+
+// workgroup-wide max / min over WAVES waves through `slot`: ONE barrier.  Call sites alternate between two slot arrays, so the
+// barrier of the next reduction separates a slot's read from its next write.
+template <int WAVES, bool MAX>
+__device__ inline unsigned pn_block_reduce(unsigned v, unsigned *slot) {
+    v = MAX ? pn_wave_max(v) : pn_wave_min(v);
+    if ((threadIdx.x & 63) == 0) slot[threadIdx.x >> 6] = v;
+    __syncthreads();
+    unsigned r = slot[0];
+#pragma unroll
+    for (int w = 1; w < WAVES; ++w) r = MAX ? max(r, slot[w]) : min(r, slot[w]);
+    return r;
+}
+
+// (the start is uniform per cloud: scalar compares and selects)
+__device__ inline int pn_clamp_start(long long s, int N) {
+    return (int)(s < 0 ? 0 : (s >= N ? N - 1 : s));
+}
+
+// ---------------------------------------------------------------------------------------------------- FPS, one workgroup
+__global__ __launch_bounds__(kFpsOneThreads) void fps_one_kernel(const float *__restrict__ xyz, int N, int npoint,
+                                                                 const long long *__restrict__ start,
+                                                                 long long *__restrict__ centroids) {
+    extern __shared__ __attribute__((aligned(16))) float pts[];          // [N][4]: x, y, z, running distance
+    __shared__ unsigned red_m[kFpsOneThreads / 64], red_i[kFpsOneThreads / 64];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float *src = xyz + (size_t)b * N * 3;
+    for (int i = tid; i < N; i += kFpsOneThreads) {
+        pts[4 * i + 0] = src[3 * i + 0];
+        pts[4 * i + 1] = src[3 * i + 1];
+        pts[4 * i + 2] = src[3 * i + 2];
+        pts[4 * i + 3] = 1e10f;
+    }
+    __syncthreads();
+    int cur = pn_clamp_start(start[b], N);
+    for (int k = 0; k < npoint; ++k) {
+        if (tid == 0) centroids[(size_t)b * npoint + k] = cur;
+        const float cx = pts[4 * cur + 0], cy = pts[4 * cur + 1], cz = pts[4 * cur + 2];
+        unsigned m = 0;
+        for (int i = tid; i < N; i += kFpsOneThreads) {
+            const float d = pn_d2(pts[4 * i + 0], pts[4 * i + 1], pts[4 * i + 2], cx, cy, cz);
+            const float nd = fminf(pts[4 * i + 3], d);
+            pts[4 * i + 3] = nd;
+            m = max(m, __float_as_uint(nd));
+        }
+        const unsigned top = pn_block_reduce<kFpsOneThreads / 64, true>(m, red_m);
+        unsigned c = 0x7fffffffu;
+        for (int i = tid; i < N; i += kFpsOneThreads) c = min(c, pn_candidate(top, __float_as_uint(pts[4 * i + 3]), (unsigned)i));
+        cur = (int)pn_block_reduce<kFpsOneThreads / 64, false>(c, red_i);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- FPS, one launch per centroid
+// workspace: dist [B][N] float, then pm [2][B][nslices] unsigned, then pi [2][B][nslices] unsigned
+__global__ __launch_bounds__(kFpsSliceThreads) void fps_slice_kernel(const float *__restrict__ xyz, int N, int npoint, int k,
+                                                                     int slice, const long long *__restrict__ start,
+                                                                     float *__restrict__ dist, unsigned *__restrict__ pm,
+                                                                     unsigned *__restrict__ pi, long long *__restrict__ centroids) {
+    __shared__ unsigned red[4][kFpsSliceThreads / 64];
+    const int b = blockIdx.y, s = blockIdx.x, nslices = gridDim.x, B = gridDim.y, tid = threadIdx.x;
+    int cur;
+    if (k == 0) {
+        cur = pn_clamp_start(start[b], N);
+    } else {
+        const unsigned *qm = pm + ((size_t)((k - 1) & 1) * B + b) * nslices;
+        const unsigned *qi = pi + ((size_t)((k - 1) & 1) * B + b) * nslices;
+        unsigned m = 0;
+        for (int j = tid; j < nslices; j += kFpsSliceThreads) m = max(m, qm[j]);
+        const unsigned top = pn_block_reduce<kFpsSliceThreads / 64, true>(m, red[0]);
+        unsigned c = 0x7fffffffu;
+        for (int j = tid; j < nslices; j += kFpsSliceThreads) c = min(c, pn_candidate(top, qm[j], qi[j]));
+        cur = (int)pn_block_reduce<kFpsSliceThreads / 64, false>(c, red[1]);
+    }
+    if (s == 0 && tid == 0) centroids[(size_t)b * npoint + k] = cur;
+    const float *src = xyz + (size_t)b * N * 3;
+    float *dd = dist + (size_t)b * N;
+    const float cx = src[3 * cur + 0], cy = src[3 * cur + 1], cz = src[3 * cur + 2];
+    const int lo = s * slice, hi = min(lo + slice, N);
+    unsigned m = 0;
+    for (int i = lo + tid; i < hi; i += kFpsSliceThreads) {
+        const float d = pn_d2(src[3 * i + 0], src[3 * i + 1], src[3 * i + 2], cx, cy, cz);
+        float prev = 1e10f;
+        if (k > 0) prev = dd[i];                                          // (uniform branch: the first launch reads nothing)
+        const float nd = fminf(prev, d);
+        dd[i] = nd;
+        m = max(m, __float_as_uint(nd));
+    }
+    const unsigned top = pn_block_reduce<kFpsSliceThreads / 64, true>(m, red[2]);
+    unsigned c = 0x7fffffffu;
+    for (int i = lo + tid; i < hi; i += kFpsSliceThreads) c = min(c, pn_candidate(top, __float_as_uint(dd[i]), (unsigned)i));
+    c = pn_block_reduce<kFpsSliceThreads / 64, false>(c, red[3]);
+    if (tid == 0) {
+        pm[((size_t)(k & 1) * B + b) * nslices + s] = top;
+        pi[((size_t)(k & 1) * B + b) * nslices + s] = c;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- ball query
+// grid (ceil(S / 4), B), one wave per query
+__global__ __launch_bounds__(256) void ball_query_kernel(const float *__restrict__ xyz, const float *__restrict__ new_xyz, int N,
+                                                         int S, float radius2, int nsample, long long *__restrict__ idx) {
+    const int lane = threadIdx.x & 63, b = blockIdx.y;
+    const int sq = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (sq >= S) return;                                                   // (wave-uniform)
+    const size_t q = (size_t)b * S + sq;
+    const float *src = xyz + (size_t)b * N * 3;
+    const float qx = new_xyz[3 * q + 0], qy = new_xyz[3 * q + 1], qz = new_xyz[3 * q + 2];
+    long long *out = idx + q * nsample;
+    int count = 0, first = N;
+    for (int base = 0; base < N && count < nsample; base += 64) {
+        const int i = base + lane, ic = min(i, N - 1);
+        const float d2 = pn_d2(src[3 * ic + 0], src[3 * ic + 1], src[3 * ic + 2], qx, qy, qz);
+        const unsigned long long in = __ballot(i < N && !(d2 > radius2));
+        const unsigned lo = (unsigned)in, hi = (unsigned)(in >> 32);
+        const int pos = count + (int)__builtin_amdgcn_mbcnt_hi(hi, __builtin_amdgcn_mbcnt_lo(lo, 0u));      // in-ball lanes below
+        if (i < N && !(d2 > radius2) && pos < nsample) out[pos] = i;         // (compared again at the use: a branch)
+        if (count == 0 && in != 0ull) first = base + (__ffsll((long long)in) - 1);     // (uniform: scalar)
+        count += __popcll(in);
+    }
+    for (int pos = min(count, nsample) + lane; pos < nsample; pos += 64) out[pos] = first;
+}
+
+// ---------------------------------------------------------------------------------------------------- grouped rows, grouped max
+// grid (S, B), block (bx, 256 / bx): a block writes the nsample rows of one group; no index arithmetic needs a division
+__global__ __launch_bounds__(256) void group_rows_kernel(const float *__restrict__ xyz, const float *__restrict__ new_xyz,
+                                                         const float *__restrict__ points, const long long *__restrict__ idx,
+                                                         int N, int S, int nsample, int D, int ld, float *__restrict__ rows) {
+    const int b = blockIdx.y;
+    const size_t bs = (size_t)b * S + blockIdx.x;
+    const float *cen = new_xyz + bs * 3;
+    for (int j = threadIdx.y; j < nsample; j += blockDim.y) {
+        const size_t row = bs * nsample + j;
+        const int id = max(0, min((int)idx[row], N - 1));
+        const float *px = xyz + ((size_t)b * N + id) * 3;
+        float *dst = rows + row * ld;
+        for (int c = threadIdx.x; c < 3; c += blockDim.x) dst[c] = __fsub_rn(px[c], cen[c]);
+        for (int c = threadIdx.x; c < D; c += blockDim.x) dst[3 + c] = points[((size_t)b * N + id) * D + c];
+        for (int c = 3 + D + threadIdx.x; c < ld; c += blockDim.x) dst[c] = 0.0f;
+    }
+}
+
+// grid (groups), 256 threads over the columns
+__global__ __launch_bounds__(256) void group_max_kernel(const float *__restrict__ rows, int ld, int nsample, int C,
+                                                        float *__restrict__ out) {
+    const size_t g = blockIdx.x;
+    for (int c = threadIdx.x; c < C; c += 256) {
+        const float *p = rows + g * nsample * ld + c;
+        float m = p[0];
+        for (int j = 1; j < nsample; ++j) m = pn_max(m, p[(size_t)j * ld]);
+        out[g * C + c] = m;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------- three nearest + interpolation
+__global__ __launch_bounds__(kNnThreads) void three_nn_kernel(const float *__restrict__ xyz1, const float *__restrict__ xyz2,
+                                                              int N, int S, long long *__restrict__ idx,
+                                                              float *__restrict__ weight) {
+    __shared__ float src[kNnChunk * 3];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int i = blockIdx.x * kNnThreads + tid, ic = min(i, N - 1);
+    const float *t = xyz1 + ((size_t)b * N + ic) * 3;
+    const float x = t[0], y = t[1], z = t[2];
+    float d0 = INFINITY, d1 = INFINITY, d2 = INFINITY;
+    int i0 = 0, i1 = 0, i2 = 0;
+    for (int base = 0; base < S; base += kNnChunk) {
+        const int n = min(kNnChunk, S - base);
+        __syncthreads();
+        for (int j = tid; j < 3 * n; j += kNnThreads) src[j] = xyz2[((size_t)b * S + base) * 3 + j];
+        __syncthreads();
+        for (int j = 0; j < n; ++j) {
+            const float d = pn_d2(x, y, z, src[3 * j + 0], src[3 * j + 1], src[3 * j + 2]);
+            const int g = base + j;
+            if (d < d2) {
+                if (d < d1) {
+                    d2 = d1; i2 = i1;
+                    if (d < d0) { d1 = d0; i1 = i0; d0 = d; i0 = g; }
+                    else { d1 = d; i1 = g; }
+                } else { d2 = d; i2 = g; }
+            }
+        }
+    }
+    if (i >= N) return;
+    const float r0 = __fdiv_rn(1.0f, __fadd_rn(d0, 1e-8f)), r1 = __fdiv_rn(1.0f, __fadd_rn(d1, 1e-8f)),
+                r2 = __fdiv_rn(1.0f, __fadd_rn(d2, 1e-8f));
+    const float norm = __fadd_rn(__fadd_rn(r0, r1), r2);
+    const size_t o = ((size_t)b * N + i) * 3;
+    idx[o + 0] = i0; idx[o + 1] = i1; idx[o + 2] = i2;
+    weight[o + 0] = __fdiv_rn(r0, norm); weight[o + 1] = __fdiv_rn(r1, norm); weight[o + 2] = __fdiv_rn(r2, norm);
+}
+
+// grid (ceil(N / 4), B), block (64, 4): four targets per block, lanes over the columns
+__global__ __launch_bounds__(256) void nn_interp_kernel(const float *__restrict__ points2, const long long *__restrict__ idx,
+                                                        const float *__restrict__ weight, int N, int S, int D,
+                                                        float *__restrict__ out) {
+    const int b = blockIdx.y, i = blockIdx.x * 4 + threadIdx.y;
+    if (i >= N) return;
+    const size_t row = (size_t)b * N + i;
+    const float *p = points2 + (size_t)b * S * D;
+    const long long *k = idx + row * 3;
+    const float *w = weight + row * 3;
+    const float *p0 = p + k[0] * D, *p1 = p + k[1] * D, *p2 = p + k[2] * D;
+    const float w0 = w[0], w1 = w[1], w2 = w[2];
+    for (int c = threadIdx.x; c < D; c += 64)
+        out[row * D + c] = __fadd_rn(__fadd_rn(__fmul_rn(p0[c], w0), __fmul_rn(p1[c], w1)), __fmul_rn(p2[c], w2));
+}
+
+// S == 1: the reference's points2.repeat(1, N, 1); same grid
+__global__ __launch_bounds__(256) void nn_repeat_kernel(const float *__restrict__ points2, int N, int D,
+                                                        long long *__restrict__ idx, float *__restrict__ weight,
+                                                        float *__restrict__ out) {
+    const int b = blockIdx.y, i = blockIdx.x * 4 + threadIdx.y;
+    if (i >= N) return;
+    const size_t row = (size_t)b * N + i;
+    for (int c = threadIdx.x; c < D; c += 64) out[row * D + c] = points2[(size_t)b * D + c];
+    if (threadIdx.x == 0) {
+        idx[row * 3 + 0] = 0; idx[row * 3 + 1] = 0; idx[row * 3 + 2] = 0;
+        weight[row * 3 + 0] = 1.0f; weight[row * 3 + 1] = 0.0f; weight[row * 3 + 2] = 0.0f;
+    }
+}
+
+static unsigned blocks_for(long long total, int per) { return (unsigned)((total + per - 1) / per); }
+
+}  // namespace t2h
+
+using namespace t2h;
+
+T2H_API size_t t2h_fps_workspace_bytes(int B, int N, int slice) {
+    if (B < 1 || N < 1 || slice < 0 || slice % 64 != 0) return 0;
+    if (slice == 0) return N <= T2H_FPS_ONE_WG_MAX ? 1 : 0;
+    const size_t nslices = ((size_t)N + slice - 1) / slice;
+    return (size_t)B * N * sizeof(float) + 4 * (size_t)B * nslices * sizeof(unsigned);
+}
+
+T2H_API int t2h_fps(const float *xyz, int B, int N, int npoint, const int64_t *start, int slice, int64_t *centroids,
+                    void *workspace, size_t workspace_bytes, t2h_stream_t stream) {
+    if (!xyz || !start || !centroids) return fail(T2H_ERR_ARG, "fps: null pointer");
+    if (B < 1 || B > 65535 || N < 1 || npoint < 1) return fail(T2H_ERR_ARG, "fps: bad shape B=%d N=%d npoint=%d", B, N, npoint);
+    if (slice < 0 || slice % 64 != 0) return fail(T2H_ERR_ARG, "fps: slice=%d must be 0 or a multiple of 64", slice);
+    hipStream_t s = as_stream(stream);
+    if (slice == 0) {
+        if (N > T2H_FPS_ONE_WG_MAX)
+            return fail(T2H_ERR_ARG, "fps: the one-workgroup form holds N <= %d points, got %d", T2H_FPS_ONE_WG_MAX, N);
+        hipLaunchKernelGGL(fps_one_kernel, dim3(B), dim3(kFpsOneThreads), (size_t)N * 16, s, xyz, N, npoint,
+                           reinterpret_cast<const long long *>(start), reinterpret_cast<long long *>(centroids));
+        note_kernel("fps_one_kernel");
+        return check_launch("fps");
+    }
+    const size_t need = t2h_fps_workspace_bytes(B, N, slice);
+    if (!workspace || workspace_bytes < need) return fail(T2H_ERR_WORKSPACE, "fps: workspace %zu < %zu bytes", workspace_bytes, need);
+    const unsigned nslices = (unsigned)(((size_t)N + slice - 1) / slice);
+    float *dist = static_cast<float *>(workspace);
+    unsigned *pm = reinterpret_cast<unsigned *>(dist + (size_t)B * N);
+    unsigned *pi = pm + 2 * (size_t)B * nslices;
+    for (int k = 0; k < npoint; ++k)
+        hipLaunchKernelGGL(fps_slice_kernel, dim3(nslices, B), dim3(kFpsSliceThreads), 0, s, xyz, N, npoint, k, slice,
+                           reinterpret_cast<const long long *>(start), dist, pm, pi, reinterpret_cast<long long *>(centroids));
+    note_kernel("fps_slice_kernel");
+    return check_launch("fps");
+}
+
+T2H_API int t2h_ball_query(const float *xyz, const float *new_xyz, int B, int N, int S, float radius2, int nsample, int64_t *idx,
+                           t2h_stream_t stream) {
+    if (!xyz || !new_xyz || !idx) return fail(T2H_ERR_ARG, "ball_query: null pointer");
+    if (B < 1 || B > 65535 || N < 1 || S < 1 || nsample < 1) return fail(T2H_ERR_ARG, "ball_query: bad shape");
+    hipLaunchKernelGGL(ball_query_kernel, dim3(blocks_for(S, 4), B), dim3(256), 0, as_stream(stream), xyz, new_xyz, N, S, radius2,
+                       nsample, reinterpret_cast<long long *>(idx));
+    note_kernel("ball_query_kernel");
+    return check_launch("ball_query");
+}
+
+T2H_API int t2h_group_rows(const float *xyz, const float *new_xyz, const float *points, const int64_t *idx, int B, int N, int S,
+                           int nsample, int D, int ld, float *rows, t2h_stream_t stream) {
+    if (!xyz || !new_xyz || !idx || !rows || (D > 0 && !points)) return fail(T2H_ERR_ARG, "group_rows: null pointer");
+    if (B < 1 || B > 65535 || N < 1 || S < 1 || nsample < 1 || D < 0 || ld < 3 + D) return fail(T2H_ERR_ARG, "group_rows: bad shape");
+    const unsigned bx = ld <= 8 ? 8u : (ld <= 32 ? 32u : 64u);
+    hipLaunchKernelGGL(group_rows_kernel, dim3(S, B), dim3(bx, 256 / bx), 0, as_stream(stream), xyz, new_xyz, points,
+                       reinterpret_cast<const long long *>(idx), N, S, nsample, D, ld, rows);
+    note_kernel("group_rows_kernel");
+    return check_launch("group_rows");
+}
+
+T2H_API int t2h_group_max(const float *rows, int ld, int64_t groups, int nsample, int C, float *out, t2h_stream_t stream) {
+    if (!rows || !out) return fail(T2H_ERR_ARG, "group_max: null pointer");
+    if (groups < 1 || groups > 0x7fffffffll || nsample < 1 || C < 1 || ld < C) return fail(T2H_ERR_ARG, "group_max: bad shape");
+    hipLaunchKernelGGL(group_max_kernel, dim3((unsigned)groups), dim3(256), 0, as_stream(stream), rows, ld, nsample, C, out);
+    note_kernel("group_max_kernel");
+    return check_launch("group_max");
+}
+
+T2H_API int t2h_three_nn_interp(const float *xyz1, const float *xyz2, const float *points2, int B, int N, int S, int D,
+                                int64_t *idx, float *weight, float *out, t2h_stream_t stream) {
+    if (!xyz1 || !xyz2 || !points2 || !idx || !weight || !out) return fail(T2H_ERR_ARG, "three_nn_interp: null pointer");
+    if (B < 1 || B > 65535 || N < 1 || S < 1 || D < 1) return fail(T2H_ERR_ARG, "three_nn_interp: bad shape");
+    if (S == 2) return fail(T2H_ERR_ARG, "three_nn_interp: S = 2 has no three neighbours (the reference fails on it too)");
+    hipStream_t s = as_stream(stream);
+    if (S == 1) {
+        hipLaunchKernelGGL(nn_repeat_kernel, dim3(blocks_for(N, 4), B), dim3(64, 4), 0, s, points2, N, D,
+                           reinterpret_cast<long long *>(idx), weight, out);
+        note_kernel("nn_repeat_kernel");
+        return check_launch("three_nn_interp");
+    }
+    hipLaunchKernelGGL(three_nn_kernel, dim3(blocks_for(N, kNnThreads), B), dim3(kNnThreads), 0, s, xyz1, xyz2, N, S,
+                       reinterpret_cast<long long *>(idx), weight);
+    hipLaunchKernelGGL(nn_interp_kernel, dim3(blocks_for(N, 4), B), dim3(64, 4), 0, s, points2, reinterpret_cast<const long long *>(idx),
+                       weight, N, S, D, out);
+    note_kernel("three_nn_kernel");
+    return check_launch("three_nn_interp");
+}

@@ -1,7 +1,7 @@
-"""Encoder registry with the reference's keys (tomosar2height/encoder/__init__.py:3-8).  The two encoders no
-reference config selects by default (``pointnet_plus_plus``, ``hourglass``) are out of the hot-path scope
- and raise a clear error instead of silently missing."""
-from . import alto, pointnet, unet
+"""Encoder registry with the reference's keys (tomosar2height/encoder/__init__.py:3-8).  ``pointnet_plus_plus`` is built for
+inference (encoder/pointnetpp.py; ``forward`` under ``train()`` raises).  ``hourglass``, which no reference config selects, is
+out of the hot-path scope and raises a clear error instead of silently missing."""
+from . import alto, pointnet, pointnetpp, unet
 
 
 class _NotBuilt:
@@ -14,7 +14,7 @@ class _NotBuilt:
 
 encoder_dict = {
     "pointnet_local_pool": pointnet.LocalPoolPointnet,
-    "pointnet_plus_plus": _NotBuilt("pointnet_plus_plus"),
+    "pointnet_plus_plus": pointnetpp.PointNetPlusPlus,
     "hourglass": _NotBuilt("hourglass"),
     "unet": unet.UNet,
 }

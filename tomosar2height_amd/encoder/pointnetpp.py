@@ -1,0 +1,227 @@
+"""PointNetPlusPlus (reference: tomosar2height/encoder/pointnetpp.py:16-173) on the MI355X path, for inference.
+
+Constructor arguments, ``state_dict`` keys and shapes are the reference's (``sa{1,2,3}`` / ``fp{3,2,1}`` with ``mlp_convs.{k}`` and
+``mlp_bns.{k}``, BatchNorm buffers and ``num_batches_tracked`` included, ``unet.*``), so a reference checkpoint loads with
+``strict=True``.  The index work -- farthest point sampling, radius grouping, grouped max, 3-nearest-neighbour propagation --
+runs on csrc/pnpp.hip (``pointops``); every 1 x 1 ``Conv2d`` / ``Conv1d`` + BatchNorm + ReLU layer is a rows x weight product on
+the fp32 MFMA kernels (``mlp.linear_fwd_`` with ``relu_out``) with the BatchNorm running statistics folded into weight and
+bias; rasterisation and the ALTO / plain U-Net are the modules the default encoder uses.
+
+Inference only.  ``forward`` under ``train()`` raises: BatchNorm batch statistics and the backward of the point stages are not
+built (DESIGN.md sections 4.9 and 8).  In ``eval()`` the point stages produce no autograd graph.
+
+The reference's inference is itself random: ``farthest_point_sample`` starts from ``torch.randint`` (pointnetpp.py:232), once
+for ``sa1`` and once for ``sa2``.  ``fps_start = None`` (default) does the same on the device, in that order -- reproducible
+under ``torch.manual_seed``, but not the reference's draws, which come from the host generator.  An ``int`` or an int64 ``[B]``
+tensor fixes the start of both levels (clamped to the level's point count); a pair ``(sa1, sa2)`` of those fixes each.
+"""
+from typing import Dict
+
+import torch
+import torch.nn as nn
+
+from .. import _lib, mlp, ops, pointops
+from ..tile import TileIndex
+from .alto import UNet as Alto
+from .unet import UNet
+
+
+def _pad4(k: int) -> int:
+    return (k + 3) // 4 * 4
+
+
+class _FoldedLayers(nn.Module):
+    """``mlp_convs`` / ``mlp_bns`` of one stage and their folded form: W' = W * s, b' = (b - mean) * s + beta with
+    s = gamma / sqrt(var + eps), computed in float64 and rounded once; the first layer's W' is padded with zero columns to the
+    row length of its input (a multiple of 4: 16-byte rows for the product kernels; K = 131 and 259 have no kernel otherwise).
+    Cached per version of every tensor involved; the cache entry carries the event behind its fill (``_lib.Ready``)."""
+
+    def _make_layers(self, conv, bn, in_channel, widths):
+        self.mlp_convs = nn.ModuleList()
+        self.mlp_bns = nn.ModuleList()
+        last = in_channel
+        for out in widths:
+            self.mlp_convs.append(conv(last, out, 1))
+            self.mlp_bns.append(bn(out))
+            last = out
+        self.__dict__["_fold"] = None
+
+    def _fold_key(self):
+        key = []
+        for conv, bn in zip(self.mlp_convs, self.mlp_bns):
+            for t in (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var):
+                key.append((t.data_ptr(), t._version))
+        return tuple(key)
+
+    def folded(self):
+        key = self._fold_key()
+        hit = self.__dict__.get("_fold")
+        if hit is not None and hit[0] == key:
+            hit[2].wait()
+            return hit[1]
+        layers = []
+        for conv, bn in zip(self.mlp_convs, self.mlp_bns):
+            _lib.require_device(conv.weight, what="PointNetPlusPlus layer")
+            s = bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps)
+            w = conv.weight.reshape(conv.weight.shape[0], -1).double() * s[:, None]
+            b = (conv.bias.double() - bn.running_mean.double()) * s + bn.bias.double()
+            wp = torch.zeros(w.shape[0], _pad4(w.shape[1]), dtype=torch.float32, device=w.device)
+            wp[:, :w.shape[1]] = w
+            layers.append((wp, b.float().contiguous()))
+        ready = _lib.Ready()
+        ready.mark()
+        self.__dict__["_fold"] = (key, layers, ready)
+        return layers
+
+    def _chain(self, rows):
+        """relu(bn(conv(.))) of every layer over [M, K] rows."""
+        with torch.no_grad():
+            for w, b in self.folded():
+                y = torch.empty(rows.shape[0], w.shape[0], dtype=torch.float32, device=rows.device)
+                mlp.linear_fwd_(rows, w, b, y, relu_out=True)
+                rows = y
+        return rows
+
+
+class PointNetSetAbstraction(_FoldedLayers):
+    def __init__(self, npoint, radius, nsample, in_channel, mlp, group_all):
+        super().__init__()
+        self.npoint, self.radius, self.nsample, self.group_all = npoint, radius, nsample, group_all
+        self._make_layers(nn.Conv2d, nn.BatchNorm2d, in_channel, mlp)
+
+    def forward_rows(self, xyz, points, start=None, trace=None):
+        """Point-major form of pointnetpp.py:31-57: ``xyz`` [B, N, 3], ``points`` [B, N, D] or None -> new_xyz [B, S, 3],
+        new_points [B, S, D'].  ``trace``: a dict that receives ``fps_idx`` and the ball ``idx``."""
+        if self.training:
+            raise NotImplementedError("PointNetSetAbstraction runs in eval() only: BatchNorm batch statistics and the backward "
+                                      "of the point stages are not built")
+        pointops._cloud(xyz, "PointNetSetAbstraction xyz")
+        b, n, _ = xyz.shape
+        d = 0 if points is None else points.shape[2]
+        ld = _pad4(3 + d)
+        with torch.no_grad():
+            if self.group_all:                                             # pointnetpp.py:303-320: a view and a concatenation
+                new_xyz = torch.zeros(b, 1, 3, dtype=torch.float32, device=xyz.device)
+                rows = torch.zeros(b * n, ld, dtype=torch.float32, device=xyz.device)
+                rows[:, :3] = xyz.reshape(b * n, 3)
+                if points is not None:
+                    rows[:, 3:3 + d] = points.reshape(b * n, d)
+                nsample = n
+            else:
+                fps_idx = pointops.farthest_point_sample(xyz, self.npoint, start)
+                new_xyz = pointops.index_points(xyz, fps_idx).contiguous()
+                idx = pointops.query_ball_point(self.radius, self.nsample, xyz, new_xyz)
+                rows = pointops.group_rows(xyz, new_xyz, points, idx, ld)
+                nsample = self.nsample
+                if trace is not None:
+                    trace["fps_idx"], trace["idx"] = fps_idx, idx
+            feat = self._chain(rows)
+            new_points = pointops.group_max_rows(feat, nsample)
+        return new_xyz, new_points.view(b, -1, new_points.shape[1])
+
+    def forward(self, xyz, points, start=None):
+        """The reference's layout: ``xyz`` [B, 3, N], ``points`` [B, D, N] -> new_xyz [B, 3, S], new_points [B, D', S]."""
+        new_xyz, new_points = self.forward_rows(xyz.permute(0, 2, 1).contiguous(),
+                                                None if points is None else points.permute(0, 2, 1).contiguous(), start)
+        return new_xyz.permute(0, 2, 1), new_points.permute(0, 2, 1)
+
+
+class PointNetFeaturePropagation(_FoldedLayers):
+    def __init__(self, in_channel, mlp):
+        super().__init__()
+        self._make_layers(nn.Conv1d, nn.BatchNorm1d, in_channel, mlp)
+
+    def forward_rows(self, xyz1, xyz2, points1, points2, trace=None):
+        """Point-major form of pointnetpp.py:70-109: targets ``xyz1`` [B, N, 3] (features ``points1`` [B, N, D1] or None), sources
+        ``xyz2`` [B, S, 3] with ``points2`` [B, S, D2] -> [B, N, D'].  ``trace`` receives the 3-NN ``idx`` and ``weight``."""
+        if self.training:
+            raise NotImplementedError("PointNetFeaturePropagation runs in eval() only: BatchNorm batch statistics and the "
+                                      "backward of the point stages are not built")
+        b, n, _ = xyz1.shape
+        with torch.no_grad():
+            interp, idx, weight = pointops.three_nn_interpolate(xyz1, xyz2, points2)
+            if trace is not None:
+                trace["idx"], trace["weight"], trace["interpolated"] = idx, weight, interp
+            rows = interp.view(b * n, -1)
+            if points1 is not None:
+                rows = torch.cat([points1.reshape(b * n, -1), rows], dim=1)
+            out = self._chain(rows)
+        return out.view(b, n, -1)
+
+    def forward(self, xyz1, xyz2, points1, points2):
+        """The reference's layout: [B, C, N] tensors in, [B, D', N] out."""
+        pm = lambda t: None if t is None else t.permute(0, 2, 1).contiguous()
+        return self.forward_rows(pm(xyz1), pm(xyz2), pm(points1), pm(points2)).permute(0, 2, 1)
+
+
+class PointNetPlusPlus(nn.Module):
+    def __init__(self, feature_dim=128, dim=3, hidden_dim=None, scatter_type=None, unet_type="alto", unet_kwargs=None,
+                 plane_resolution=None):
+        super().__init__()
+        self.sa1 = PointNetSetAbstraction(npoint=512, radius=0.2, nsample=32, in_channel=dim + 3, mlp=[64, 64, 128], group_all=False)
+        self.sa2 = PointNetSetAbstraction(npoint=128, radius=0.4, nsample=64, in_channel=128 + 3, mlp=[128, 128, 256], group_all=False)
+        self.sa3 = PointNetSetAbstraction(npoint=None, radius=None, nsample=None, in_channel=256 + 3, mlp=[256, 512, 1024], group_all=True)
+        self.fp3 = PointNetFeaturePropagation(in_channel=1280, mlp=[256, 256])
+        self.fp2 = PointNetFeaturePropagation(in_channel=384, mlp=[256, 128])
+        self.fp1 = PointNetFeaturePropagation(in_channel=128, mlp=[128, 128, feature_dim])
+        self.unet_type = unet_type
+        self.feature_dim = feature_dim
+        if unet_type == "unet":
+            self.unet = UNet(feature_dim, in_channels=feature_dim, **(unet_kwargs or {}))
+        elif unet_type == "alto":
+            self.unet = Alto(feature_dim, in_channels=feature_dim, **(unet_kwargs or {}))
+        else:
+            raise ValueError(f"Unknown unet_type: {unet_type}")
+        self.reso_plane = plane_resolution
+        self.channels_last = False
+        self.fps_start = None          # see the module docstring
+
+    def set_channels_last(self, flag: bool):
+        """Keep the grid side in channels_last memory so planes need no NCHW<->NHWC copies."""
+        self.channels_last = bool(flag)
+        if hasattr(self.unet, "set_channels_last"):
+            self.unet.set_channels_last(flag)
+
+    def _starts(self):
+        s = self.fps_start
+        return tuple(s) if isinstance(s, (tuple, list)) else (s, s)
+
+    def point_features(self, xyz: torch.Tensor, targets: torch.Tensor = None, trace: dict = None) -> torch.Tensor:
+        """pointnetpp.py:152-163: ``xyz`` [B, N, dim] -> per-point features [B, N', feature_dim] at ``targets`` [B, N', 3]
+        (default: the cloud itself, in its own order).  The last propagation is independent per target, so the encoder asks
+        for the features in the cell-sorted order of its tile index.  ``trace``: a dict that receives every level's tensors."""
+        tr = (lambda k: trace.setdefault(k, {})) if trace is not None else (lambda k: None)
+        l0_xyz = xyz[:, :, :3].contiguous()
+        s1, s2 = self._starts()
+        l1_xyz, l1_points = self.sa1.forward_rows(l0_xyz, xyz, s1, tr("sa1"))       # (the order of the draws: sa1, then sa2)
+        l2_xyz, l2_points = self.sa2.forward_rows(l1_xyz, l1_points, s2, tr("sa2"))
+        l3_xyz, l3_points = self.sa3.forward_rows(l2_xyz, l2_points)
+        l2_points = self.fp3.forward_rows(l2_xyz, l3_xyz, l2_points, l3_points, tr("fp3"))
+        l1_points = self.fp2.forward_rows(l1_xyz, l2_xyz, l1_points, l2_points, tr("fp2"))
+        l0_points = self.fp1.forward_rows(l0_xyz if targets is None else targets, l1_xyz, None, l1_points, tr("fp1"))
+        if trace is not None:
+            trace.update(l1_points=l1_points, l2_points=l2_points, l3_points=l3_points, l0_points=l0_points)
+        return l0_points
+
+    def forward(self, xyz: torch.Tensor, trace: dict = None) -> Dict[str, torch.Tensor]:
+        """``xyz`` [B, N, dim] in [0, 1) -> ``{'xy': [B, feature_dim, R, R]}``."""
+        if self.training:
+            raise NotImplementedError("PointNetPlusPlus runs in eval() only: training needs BatchNorm batch statistics and the "
+                                      "backward of farthest point sampling, grouping and 3-NN propagation, which are not built")
+        pointops._cloud(xyz, "PointNetPlusPlus", cols=None)
+        xyz = xyz.contiguous()
+        b, n, dim = xyz.shape
+        tile = TileIndex(xyz, self.reso_plane)
+        targets = tile.pts.view(b, n, dim)[:, :, :3].contiguous()
+        net = self.point_features(xyz, targets, trace).view(b * n, self.feature_dim)        # rows in the tile's sorted order
+        if trace is not None:
+            trace["tile"] = tile
+        if self.unet_type == "alto":
+            plane, net = ops.rasterise_mean_thru(tile, net, self.reso_plane, self.channels_last)     # pointnetpp.py:166
+            out = {"xy": self.unet.forward_sorted(tile, plane, net)}                                 # pointnetpp.py:171
+        else:
+            plane = ops.rasterise_mean(tile, net, self.reso_plane, self.channels_last)
+            out = {"xy": self.unet(plane)}
+        if trace is not None:
+            trace["plane"] = plane
+        return out

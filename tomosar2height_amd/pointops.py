@@ -1,0 +1,204 @@
+"""PointNet++ point operators on the MI355X (reference: tomosar2height/encoder/pointnetpp.py:220-320 and :90-97): farthest
+point sampling, radius grouping, grouped rows, grouped max and 3-nearest-neighbour interpolation over csrc/pnpp.hip.
+
+Argument order and result shapes are the reference's; tensors are point-major (``[B, N, C]``), as the reference's helpers take
+them.  Forward only: results carry no autograd graph.  There is no CPU path: a tensor that is not on
+the device raises.
+
+Squared distances are taken by differences in fp32, ``(dx*dx + dy*dy) + dz*dz``; the reference's matmul form rounds
+differently within a few ulps of 6 at unit coordinates, which can move a point that lies that close to a ball's boundary, or
+reorder two neighbours that close to equidistant.  Ties are broken by the lowest index everywhere (FPS maxima, 3-NN distances);
+the reference leaves them to ``torch.max`` / an unstable ``sort``.
+
+The entry points are declared in include/t2h_pnpp.h and typed here (``SIGNATURES``), not in ``_lib.SIGNATURES``.
+"""
+import ctypes
+import numbers
+import os
+
+import torch
+
+from . import _lib
+
+_vp, _i, _i64, _sz, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
+
+# name -> (restype, argtypes); mirrors include/t2h_pnpp.h one to one
+SIGNATURES = {
+    "t2h_fps_workspace_bytes": (_sz, [_i, _i, _i]),
+    "t2h_fps": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _sz, _vp]),
+    "t2h_ball_query": (_i, [_vp, _vp, _i, _i, _i, _f, _i, _vp, _vp]),
+    "t2h_group_rows": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "t2h_group_max": (_i, [_vp, _i, _i64, _i, _i, _vp, _vp]),
+    "t2h_three_nn_interp": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+}
+
+FPS_ONE_WG_MAX = 2048       # T2H_FPS_ONE_WG_MAX
+# T2H_FPS_SLICE: points per workgroup of the sliced FPS (one launch per centroid).  Unset: clouds of up to FPS_ONE_WG_MAX points
+# take the one-workgroup form and larger ones slices of FPS_SLICE_DEFAULT; set (a multiple of 64), EVERY cloud takes the sliced
+# form with that slice -- how a test runs it on a small cloud.  Both forms give the same bytes.
+FPS_SLICE_DEFAULT = 1024
+
+_typed = False
+
+
+def load():
+    """The library handle with the PointNet++ entries typed (untyped ctypes calls would truncate 64-bit pointers)."""
+    global _typed
+    lib = _lib.load()
+    if not _typed:
+        for name, (res, args) in SIGNATURES.items():
+            try:
+                fn = getattr(lib, name)
+            except AttributeError as e:
+                raise _lib.T2HLibraryError(f"{_lib.LIB_PATH} does not export {name}; rebuild it") from e
+            fn.restype, fn.argtypes = res, args
+        _typed = True
+    return lib
+
+
+def fps_slice(n: int) -> int:
+    """Points per workgroup ``farthest_point_sample`` will use on an N-point cloud (0: the one-workgroup form)."""
+    env = os.environ.get("T2H_FPS_SLICE")
+    if env:
+        s = int(env)
+        if s < 64 or s % 64:
+            raise ValueError(f"T2H_FPS_SLICE={env}: a multiple of 64 is needed")
+        return s
+    return 0 if n <= FPS_ONE_WG_MAX else FPS_SLICE_DEFAULT
+
+
+def fps_launches(n: int, npoint: int) -> int:
+    return 1 if fps_slice(n) == 0 else npoint
+
+
+def _cloud(t, what, cols=3):
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{what}: expected a torch tensor, got {type(t).__name__}")
+    _lib.require_device(t, what=what)
+    if t.dtype != torch.float32:
+        raise TypeError(f"{what}: float32 expected, got {t.dtype}")
+    if t.dim() != 3 or (cols is not None and t.shape[2] != cols) or t.shape[1] < 1 or t.shape[0] < 1:
+        raise ValueError(f"{what}: expected [B, N, {cols if cols is not None else 'C'}], got {tuple(t.shape)}")
+    return t
+
+
+def fps_start(start, b: int, n: int, device) -> torch.Tensor:
+    """``start`` of ``farthest_point_sample`` as an int64 [B] device tensor: None draws ``torch.randint(0, N, (B,))`` on the
+    device (pointnetpp.py:232), an int is used for every cloud, a tensor is taken as it is."""
+    if start is None:
+        return torch.randint(0, n, (b,), dtype=torch.long, device=device)
+    if isinstance(start, numbers.Integral):
+        return torch.full((b,), int(start), dtype=torch.long, device=device)
+    if not isinstance(start, torch.Tensor):
+        raise TypeError(f"fps start: expected None, an integer or an int64 [{b}] tensor, got {type(start).__name__}")
+    if start.dtype != torch.long or tuple(start.shape) != (b,):
+        raise ValueError(f"fps start: expected an int64 [{b}] tensor, got {start.dtype} {tuple(start.shape)}")
+    _lib.require_device(start, what="fps start")
+    return start
+
+
+def farthest_point_sample(xyz: torch.Tensor, npoint: int, start=None) -> torch.Tensor:
+    """pointnetpp.py:220-241: ``xyz`` [B, N, 3] -> centroid indices [B, npoint] int64.  ``start``: see ``fps_start``; on equal
+    maxima the next centroid is the lowest index of the maximum."""
+    _cloud(xyz, "farthest_point_sample")
+    lib = load()
+    b, n, _ = xyz.shape
+    start = fps_start(start, b, n, xyz.device)
+    out = torch.empty(b, npoint, dtype=torch.long, device=xyz.device)
+    slice_ = fps_slice(n)
+    nws = int(lib.t2h_fps_workspace_bytes(b, n, slice_))
+    ws = _lib.workspace(nws, xyz.device)
+    _lib.call("t2h_fps", _lib.ptr(xyz), b, n, npoint, _lib.ptr(start), slice_, _lib.ptr(out), _lib.ptr(ws), nws, _lib.stream(),
+              nbytes=b * n * (12 + (8 * npoint if slice_ else 0)), flops=9 * b * n * npoint)
+    return out
+
+
+def index_points(points: torch.Tensor, idx: torch.Tensor) -> torch.Tensor:
+    """pointnetpp.py:200-217 for ``idx`` [B, S]: rows of ``points`` [B, N, C] -> [B, S, C] (a torch gather: plumbing)."""
+    return torch.gather(points, 1, idx.unsqueeze(-1).expand(-1, -1, points.shape[2]))
+
+
+def query_ball_point(radius: float, nsample: int, xyz: torch.Tensor, new_xyz: torch.Tensor) -> torch.Tensor:
+    """pointnetpp.py:244-264: per query the first ``nsample`` indices, in index order, within ``radius`` -> [B, S, nsample] int64,
+    padded with the first.  The threshold is ``radius ** 2`` rounded to fp32."""
+    _cloud(xyz, "query_ball_point xyz")
+    _cloud(new_xyz, "query_ball_point new_xyz")
+    load()
+    b, n, _ = xyz.shape
+    s = new_xyz.shape[1]
+    idx = torch.empty(b, s, nsample, dtype=torch.long, device=xyz.device)
+    _lib.call("t2h_ball_query", _lib.ptr(xyz), _lib.ptr(new_xyz), b, n, s, float(radius) ** 2, nsample, _lib.ptr(idx), _lib.stream(),
+              nbytes=12 * b * (n + s) + 8 * b * s * nsample)
+    return idx
+
+
+def group_rows(xyz, new_xyz, points, idx, ld=None) -> torch.Tensor:
+    """Rows [B * S * nsample, ld] = grouped xyz minus the centroid | grouped features | zeros (``ld`` >= 3 + D: the row length
+    the layers' products want, a multiple of 4)."""
+    load()
+    b, n, _ = xyz.shape
+    _, s, ns = idx.shape
+    d = 0 if points is None else points.shape[2]
+    ld = 3 + d if ld is None else ld
+    rows = torch.empty(b * s * ns, ld, dtype=torch.float32, device=xyz.device)
+    _lib.call("t2h_group_rows", _lib.ptr(xyz), _lib.ptr(new_xyz), None if points is None else _lib.ptr(points), _lib.ptr(idx), b, n,
+              s, ns, d, ld, _lib.ptr(rows), _lib.stream(), nbytes=b * s * ns * (8 + 4 * (3 + d) + 4 * ld))
+    return rows
+
+
+def sample_and_group(npoint, radius, nsample, xyz, points, returnfps=False, start=None):
+    """pointnetpp.py:267-300: -> new_xyz [B, npoint, 3], new_points [B, npoint, nsample, 3 + D] (with ``returnfps`` also the
+    grouped xyz and the FPS indices, as the reference)."""
+    _cloud(xyz, "sample_and_group xyz")
+    if points is not None:
+        _cloud(points, "sample_and_group points", cols=None)
+    b = xyz.shape[0]
+    fps_idx = farthest_point_sample(xyz, npoint, start)
+    new_xyz = index_points(xyz, fps_idx).contiguous()
+    idx = query_ball_point(radius, nsample, xyz, new_xyz)
+    new_points = group_rows(xyz, new_xyz, points, idx).view(b, npoint, nsample, -1)
+    if returnfps:
+        grouped_xyz = torch.gather(xyz, 1, idx.view(b, -1, 1).expand(-1, -1, 3)).view(b, npoint, nsample, 3)
+        return new_xyz, new_points, grouped_xyz, fps_idx
+    return new_xyz, new_points
+
+
+def group_max_rows(rows: torch.Tensor, nsample: int, c: int = None) -> torch.Tensor:
+    """[groups * nsample, ld] rows -> [groups, c]: the max over each group's rows (columns 0 .. c)."""
+    load()
+    _lib.require_device(rows, what="group_max")
+    c = rows.shape[1] if c is None else c
+    groups = rows.shape[0] // nsample
+    out = torch.empty(groups, c, dtype=torch.float32, device=rows.device)
+    _lib.call("t2h_group_max", _lib.ptr(rows), rows.stride(0), groups, nsample, c, _lib.ptr(out), _lib.stream(),
+              nbytes=4 * c * (rows.shape[0] + groups))
+    return out
+
+
+def group_max(new_points: torch.Tensor) -> torch.Tensor:
+    """``torch.max(new_points, 2)[0]`` of pointnetpp.py:55 on point-major groups: [B, S, nsample, C] -> [B, S, C]."""
+    if not isinstance(new_points, torch.Tensor) or new_points.dim() != 4:
+        raise ValueError("group_max: expected [B, S, nsample, C]")
+    _lib.require_device(new_points, what="group_max")
+    b, s, ns, c = new_points.shape
+    return group_max_rows(new_points.view(b * s * ns, c), ns).view(b, s, c)
+
+
+def three_nn_interpolate(xyz1: torch.Tensor, xyz2: torch.Tensor, points2: torch.Tensor):
+    """pointnetpp.py:87-97: features ``points2`` [B, S, D] at ``xyz2`` [B, S, 3] interpolated to ``xyz1`` [B, N, 3] with
+    inverse-square-distance weights over the three nearest sources -> (interpolated [B, N, D], idx [B, N, 3] int64, weight
+    [B, N, 3]).  ``S == 1`` repeats the one source row (idx 0, weight 1, 0, 0)."""
+    _cloud(xyz1, "three_nn_interpolate xyz1")
+    _cloud(xyz2, "three_nn_interpolate xyz2")
+    _cloud(points2, "three_nn_interpolate points2", cols=None)
+    load()
+    b, n, _ = xyz1.shape
+    s, d = xyz2.shape[1], points2.shape[2]
+    if points2.shape[:2] != xyz2.shape[:2] or xyz2.shape[0] != b:
+        raise ValueError("three_nn_interpolate: xyz2 and points2 must share [B, S]")
+    idx = torch.empty(b, n, 3, dtype=torch.long, device=xyz1.device)
+    weight = torch.empty(b, n, 3, dtype=torch.float32, device=xyz1.device)
+    out = torch.empty(b, n, d, dtype=torch.float32, device=xyz1.device)
+    _lib.call("t2h_three_nn_interp", _lib.ptr(xyz1), _lib.ptr(xyz2), _lib.ptr(points2), b, n, s, d, _lib.ptr(idx), _lib.ptr(weight),
+              _lib.ptr(out), _lib.stream(), nbytes=b * n * (12 + 36 + 16 * d) + b * s * 12, flops=b * n * (9 * s + 5 * d))
+    return out, idx, weight
