@@ -36,8 +36,8 @@ int t2h_inst_label(const uint8_t *mask, int ld, int R, int C, int connectivity, 
                    void *workspace, size_t workspace_bytes, t2h_stream_t stream);
 
 /* n = H * W pixels, K labels.  Linear in n and K: 256 + 12 * K + 8 * ceil(K / 1024) bytes of per-label tables, 8 * n
- * bytes of compacted (label, key) pairs, and (24 + 8 192) bytes for each of the at most n / (T2H_INST_SMALL_MAX + 1) + 1
- * segments that can be large (about 4 bytes per pixel), each part rounded up to 256.  0 for a shape the entry would refuse. */
+ * bytes of compacted (label, key) pairs, and (24 + 2 048) bytes for each of the at most n / (T2H_INST_SMALL_MAX + 1) + 1
+ * segments that can be large (about 1 byte per pixel), each part rounded up to 256.  0 for a shape the entry would refuse. */
 size_t t2h_inst_medians_workspace_bytes(int64_t n, int K);
 
 /* counts[k-1] = |{labels == k}| and medians[k-1] = np.median(values32[labels == k]) for k = 1..K, where values32 is the

@@ -294,6 +294,51 @@ def test_permuted_points_give_the_same_bytes():
     assert runs[0] == runs[1] == runs[2]
 
 
+def float32_segments(seed=31):
+    """Every size class of both key widths as float32 values that are multiples of 0.25 below 2^10: the mean of any two is a
+    multiple of 0.125 and a float32, so np.median is exact in float32 and in float64 and no double rounding can enter."""
+    rng = np.random.default_rng(seed)
+    sizes = (1, 2, 64, 65, 2048, 2049, 4097, 9001)
+    segments = [(np.round(rng.standard_normal(n) * 64) / 4 + 0.0).astype(np.float32) for n in sizes]   # (+ 0.0: no -0.0)
+    segments[1][:] = (-1.5, 2.25)                                                # even count, opposite-signed middle pair
+    segments[3][:] = -0.0                                                        # only negative zeros
+    segments[4] = np.r_[-np.abs(segments[4][:1024]) - 0.25, np.abs(segments[4][1024:]) + 0.25][rng.permutation(2048)]
+    segments[5][rng.integers(2049)] = np.nan
+    return segments
+
+
+def test_raster_and_cloud_medians_are_one_algorithm():
+    """The float32 entry (segment_medians, 32-bit keys) and the float64 entry (point_medians, 64-bit keys) on the same
+    segments: equal counts, and the raster medians are the cloud medians rounded once to float32, bit for bit."""
+    from tomosar2height_amd import point_medians, segment_medians
+    segments = float32_segments()
+    K, total = len(segments), sum(s.size for s in segments)
+    with np.errstate(invalid="ignore"):
+        want32 = np.array([np.median(s) for s in segments], np.float32)
+        want64 = np.array([np.median(s.astype(np.float64)) for s in segments], np.float64)
+    nan = np.isnan(want64)
+    assert nan.tolist() == [k == 5 for k in range(K)] and np.isnan(want32).tolist() == nan.tolist()
+    assert want32[~nan].tobytes() == want64[~nan].astype(np.float32).tobytes()   # the inputs allow the comparison below
+    middle = np.sort(segments[4])[1023:1025]
+    assert want64[1] == 0.375 and middle[0] < 0 < middle[1] and want64[3].tobytes() == np.float64(0.0).tobytes()
+
+    H, W = 131, 133                                                              # 17 423 pixels for 17 327 values
+    values = np.zeros(H * W, np.float32)
+    labels = np.zeros(H * W, np.int32)
+    values[:total] = np.concatenate(segments)
+    labels[:total] = np.concatenate([np.full(s.size, k, np.int32) for k, s in enumerate(segments, 1)])
+    counts_r, med_r = segment_medians(to_dev(values.reshape(H, W)), to_dev(labels.reshape(H, W)), K)
+    order = np.random.default_rng(32).permutation(H * W)
+    counts_c, med_c = point_medians(to_dev(values.astype(np.float64)[order]), to_dev(labels[order]), K)
+    assert med_r.dtype == torch.float32 and med_c.dtype == torch.float64
+    counts_r, med_r, counts_c, med_c = (t.cpu().numpy() for t in (counts_r, med_r, counts_c, med_c))
+    print(counts_r.tolist(), med_r.tolist(), med_c.tolist())
+    assert counts_r.tolist() == counts_c.tolist() == [s.size for s in segments]
+    assert np.isnan(med_r).tolist() == np.isnan(med_c).tolist() == nan.tolist()
+    assert med_r[~nan].tobytes() == med_c[~nan].astype(np.float32).tobytes()
+    assert med_r[~nan].tobytes() == want32[~nan].tobytes() and med_c[~nan].tobytes() == want64[~nan].tobytes()
+
+
 def test_module_loads_alone_in_a_fresh_process():
     """Nothing but cloud_instances is imported: its load() must type what the labels (an int32 mask goes through the
     evaluator's predicate) and the raster medians call."""

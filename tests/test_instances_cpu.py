@@ -125,7 +125,7 @@ def test_inst_entries_reject_bad_arguments_without_a_gpu():
     assert b"workspace" in lib.t2h_last_error_string()
     # linear in the pixels: the documented constants bound the Berlin chunk's workspace
     n_px, K = 1660 * 1990, 5000
-    assert lib.t2h_inst_medians_workspace_bytes(n_px, K) <= 8 * n_px + (n_px // 2049 + 1) * (24 + 8192) + 12 * K + 8 * 5 + 12 * 256
+    assert lib.t2h_inst_medians_workspace_bytes(n_px, K) <= 8 * n_px + (n_px // 2049 + 1) * (24 + 2048) + 12 * K + 8 * 5 + 12 * 256
     # K = 0 is valid and launches nothing
     assert lib.t2h_inst_medians(p, 0, 8, 8, 8, p, 0, p, p, p, big, n) == 0
 

@@ -30,12 +30,10 @@
 // prefix tests of the select are plain compares used at once.
 #include <math.h>
 
-#include "t2h_common.h"
+#include "dsm_common.h"
 #include "../../include/t2h_eval.h"
 
 namespace t2h {
-
-typedef unsigned long long u64;
 
 constexpr int kEvalClasses = T2H_EVAL_MAX_CLASSES;
 constexpr int kEvalBins = 256;                                   // 8-bit digits
@@ -51,14 +49,6 @@ struct EvalState {                                               // lives in the
     u64 cnt[kEvalClasses];
     double med[kEvalClasses];
 };
-
-__device__ inline u64 eval_key(double v) {                       // order-preserving image: a < b  <=>  key(a) < key(b)
-    u64 b = (u64)__double_as_longlong(v);
-    return b ^ ((u64)((long long)b >> 63) | 0x8000000000000000ull);
-}
-__device__ inline double eval_value(u64 k) {
-    return __longlong_as_double((long long)(k ^ ((u64)((long long)~k >> 63) | 0x8000000000000000ull)));
-}
 
 // ------------------------------------------------------------------------------------------ construction-time planes
 template <typename T>
@@ -247,10 +237,10 @@ __global__ __launch_bounds__(256) void eval_select_pass_kernel(const double *__r
     auto take = [&](double r, unsigned bits) {
         if (bits == 0) return;
         u64 key[2];
-        if (ROUND == 0) { key[0] = eval_key(r); key[1] = eval_key(fabs(r)); }
+        if (ROUND == 0) { key[0] = key64(r); key[1] = key64(fabs(r)); }
         for (int c = 0; c < ncls; ++c) {
             if (!((bits >> c) & 1u)) continue;
-            if (ROUND == 1) key[0] = eval_key(fabs(r - st->med[c]));
+            if (ROUND == 1) key[0] = key64(fabs(r - st->med[c]));
 #pragma unroll
             for (int s = 0; s < S; ++s) {
                 const int i = (c * S + s) * 2;
@@ -318,7 +308,7 @@ __global__ __launch_bounds__(64) void eval_select_scan_kernel(const u64 *__restr
 }
 
 __device__ inline double eval_middle(u64 klo, u64 khi) {
-    double lo = eval_value(klo), hi = eval_value(khi);
+    double lo = value64(klo), hi = value64(khi);
     return klo == khi ? lo : (lo + hi) / 2.0;
 }
 
@@ -354,10 +344,6 @@ static int eval_stat_wgs(int64_t n) {
     if (g < need) g = need;
     return (int)(g < 1 ? 1 : g);
 }
-static int eval_flat_wgs(int64_t n, int cap) {
-    int64_t g = (n + 255) / 256;
-    return (int)(g < 1 ? 1 : g > cap ? cap : g);
-}
 constexpr size_t kEvalHistBytes = (size_t)2 * kEvalPasses * kEvalHistBins * sizeof(u64);
 constexpr size_t kEvalStateBytes = (sizeof(EvalState) + 255) / 256 * 256;
 constexpr int64_t kEvalMaxPixels = (int64_t)1 << 40;
@@ -372,7 +358,7 @@ T2H_API int t2h_eval_predicate(const void *src, int kind, int op, double value, 
     if (n < 1 || n > kEvalMaxPixels) return fail(T2H_ERR_ARG, "eval_predicate: bad size %lld", (long long)n);
     if (kind < T2H_EVAL_U8 || kind > T2H_EVAL_F64 || op < T2H_EVAL_NONZERO || op > T2H_EVAL_GT)
         return fail(T2H_ERR_ARG, "eval_predicate: unknown element kind %d or predicate %d", kind, op);
-    dim3 grid(eval_flat_wgs(n, 2048)), block(256);
+    dim3 grid(flat_wgs(n, 2048)), block(256);
     hipStream_t s = as_stream(stream);
 #define T2H_EVAL_PRED(T) \
     hipLaunchKernelGGL(eval_predicate_kernel<T>, grid, block, 0, s, (const T *)src, op, value, out, (long long)n)
@@ -405,7 +391,7 @@ T2H_API int t2h_eval_class_bits(const uint8_t *mask, int invert, const uint8_t *
     if (n < 1 || n > kEvalMaxPixels) return fail(T2H_ERR_ARG, "eval_class_bits: bad size %lld", (long long)n);
     if (bit < 0 || bit >= T2H_EVAL_MAX_CLASSES || (invert != 0 && invert != 1))
         return fail(T2H_ERR_ARG, "eval_class_bits: bit %d (0 .. %d) / invert %d (0, 1)", bit, T2H_EVAL_MAX_CLASSES - 1, invert);
-    hipLaunchKernelGGL(eval_class_bits_kernel, dim3(eval_flat_wgs(n, 2048)), dim3(256), 0, as_stream(stream), mask, invert,
+    hipLaunchKernelGGL(eval_class_bits_kernel, dim3(flat_wgs(n, 2048)), dim3(256), 0, as_stream(stream), mask, invert,
                        gt_mask, bit, cls, (long long)n);
     return check_launch("eval_class_bits");
 }
@@ -461,7 +447,7 @@ T2H_API int t2h_eval_stats(const double *diff, const uint16_t *cw, int64_t n, in
         hipLaunchKernelGGL(eval_stats_kernel<16>, dim3(wgs), dim3(256), 0, s, diff, cw, (long long)n, slab);
     hipLaunchKernelGGL(eval_stats_finalize_kernel, dim3(ncls), dim3(256), 0, s, slab, wgs, table, st);
 
-    const int swgs = eval_flat_wgs((n + 1) / 2, kEvalSelectWgsCap);
+    const int swgs = flat_wgs((n + 1) / 2, kEvalSelectWgsCap);
     for (int round = 0; round < 2; ++round) {
         const int S = round == 0 ? 2 : 1;
         const size_t lds = (size_t)ncls * S * 2 * kEvalBins * sizeof(unsigned);

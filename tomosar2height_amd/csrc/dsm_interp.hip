@@ -23,7 +23,7 @@
 // is loaded, never beside a training step, so the rule for kernels that share a CU with the split convolutions does not bind.
 #include <math.h>
 
-#include "t2h_common.h"
+#include "dsm_common.h"
 #include "../../include/t2h_interp.h"
 
 namespace t2h {
@@ -35,25 +35,6 @@ constexpr int kIpCols = T2H_INTERP_TABLE_COLS;
 constexpr int kIpScanBlock = 1024;                                // items per workgroup of the scans (4 per thread)
 constexpr int kIpPartials = 1024;                                 // workgroups of the bounds pass
 constexpr int64_t kIpMaxPoints = 0x7fffffff;
-
-// exclusive prefix of v over the 256 threads of the workgroup (thread order) and the workgroup's total
-__device__ inline int ip_block_scan(int v, int *total) {
-    __shared__ int wsum[4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        int up = __shfl_up(incl, off);
-        if (lane >= off) incl += up;
-    }
-    __syncthreads();                                              // (a previous call's readers are done with wsum)
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int base = 0;
-    for (int w = 0; w < wave; ++w) base += wsum[w];
-    *total = wsum[0] + wsum[1] + wsum[2] + wsum[3];
-    return base + incl - v;
-}
 
 // the cell of coordinate v along one axis: floor((v - vmin) / h), clamped to 0 .. g - 1 (v == vmax lands in the last cell).
 // Monotone in v, and the same expression for points and for grid nodes.
@@ -150,17 +131,8 @@ __global__ __launch_bounds__(256) void interp_scan_sums_kernel(const int *__rest
     for (int j = 0; j < 4; ++j)
         if (base + j < n) s += in[base + j];
     int total;
-    ip_block_scan(s, &total);
+    block_scan(s, &total);
     if (threadIdx.x == 0) bsum[blockIdx.x] = total;
-}
-
-// one workgroup: a[0 .. nb) to its exclusive prefix in place
-__global__ __launch_bounds__(256) void interp_scan_top_kernel(int *__restrict__ a, int nb) {
-    const int per = (nb + 255) / 256, lo = min(nb, (int)threadIdx.x * per), hi = min(nb, lo + per);
-    int sum = 0;
-    for (int i = lo; i < hi; ++i) sum += a[i];
-    int tot, run = ip_block_scan(sum, &tot);
-    for (int i = lo; i < hi; ++i) { int t = a[i]; a[i] = run; run += t; }
 }
 
 // out[i] = in[0] + ... + in[i - 1]  (out may be in: a thread reads its four items before it writes them)
@@ -172,7 +144,7 @@ __global__ __launch_bounds__(256) void interp_scan_write_kernel(const int *in, l
         c[j] = base + j < n ? in[base + j] : 0;
         s += c[j];
     }
-    int total, run = ip_block_scan(s, &total) + bsum[blockIdx.x];
+    int total, run = block_scan(s, &total) + bsum[blockIdx.x];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         if (base + j < n) out[base + j] = run;
@@ -385,7 +357,6 @@ __global__ __launch_bounds__(256) void interp_search_kernel(const double *__rest
 }
 
 // ------------------------------------------------------------------------------------------ host side
-static size_t ip_up256(size_t b) { return (b + 255) / 256 * 256; }
 static int64_t ip_cells_cap(int64_t N) { return N / 2 + 8; }
 static unsigned ip_wgs(int64_t n) { return (unsigned)((n + 255) / 256); }
 
@@ -395,18 +366,18 @@ struct IpIndexLayout {                                            // byte offset
         const size_t n = (size_t)N, cap = (size_t)ip_cells_cap(N);
         const size_t items = (n + 1 > cap + 1 ? n + 1 : cap + 1), nb = (items + kIpScanBlock - 1) / kIpScanBlock;
         cnt = 0;
-        bsum = cnt + ip_up256(4 * (cap + 1));
-        tmp = bsum + ip_up256(4 * nb);
-        sorted = tmp + ip_up256(24 * n);
-        pos = sorted + ip_up256(24 * n);
-        end = pos + ip_up256(4 * (n + 1));
+        bsum = cnt + up256(4 * (cap + 1));
+        tmp = bsum + up256(4 * nb);
+        sorted = tmp + up256(24 * n);
+        pos = sorted + up256(24 * n);
+        end = pos + up256(4 * (n + 1));
     }
 };
 
 static void ip_scan(const int *in, int64_t n, int *bsum, int *out, hipStream_t s) {
     const int nb = (int)((n + kIpScanBlock - 1) / kIpScanBlock);
     hipLaunchKernelGGL(interp_scan_sums_kernel, dim3(nb), dim3(256), 0, s, in, (long long)n, bsum);
-    hipLaunchKernelGGL(interp_scan_top_kernel, dim3(1), dim3(256), 0, s, bsum, nb);
+    hipLaunchKernelGGL(scan_top_kernel, dim3(1), dim3(256), 0, s, bsum, (int *)nullptr, nb, (int *)nullptr);
     hipLaunchKernelGGL(interp_scan_write_kernel, dim3(nb), dim3(256), 0, s, in, (long long)n, (const int *)bsum, out);
 }
 

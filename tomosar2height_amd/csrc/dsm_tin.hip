@@ -26,7 +26,7 @@
 // beside a training step, so the rule for kernels that share a CU with the split convolutions does not bind.
 #include <math.h>
 
-#include "t2h_common.h"
+#include "dsm_common.h"
 #include "tin_core.h"
 #include "../../include/t2h_tin.h"
 
@@ -347,7 +347,6 @@ __global__ __launch_bounds__(256) void tin_search_kernel(const double *__restric
 }
 
 // ------------------------------------------------------------------------------------------ host side
-static size_t tin_up256(size_t b) { return (b + 255) / 256 * 256; }
 
 struct TinHullLayout {                                            // byte offsets into the workspace
     size_t counter, poly, part_v, part_i, surv, end;
@@ -357,10 +356,10 @@ struct TinHullLayout {                                            // byte offset
         while (cap < M) cap <<= 1;                                // M <= 2^30
         counter = 0;
         poly = 256;
-        part_v = poly + tin_up256(8 * (1 + 2 * kTinDirs));
-        part_i = part_v + tin_up256((size_t)8 * kTinPartials * kTinDirs);
-        surv = part_i + tin_up256((size_t)4 * kTinPartials * kTinDirs);
-        end = surv + tin_up256((size_t)4 * cap);
+        part_v = poly + up256(8 * (1 + 2 * kTinDirs));
+        part_i = part_v + up256((size_t)8 * kTinPartials * kTinDirs);
+        surv = part_i + up256((size_t)4 * kTinPartials * kTinDirs);
+        end = surv + up256((size_t)4 * cap);
     }
 };
 constexpr int64_t kTinMaxHullPoints = 1 << 30;
