@@ -12,7 +12,9 @@
 //     m  = m + (g - m) * (1 - beta1)                      (Tensor.lerp_, weight < 0.5 branch)
 //     v  = v * beta2 + (1 - beta2) * g * g                (mul_ then addcmul_)
 //     p  = p + (-(lr / bc1)) * (m / (sqrt(v) / sqrt(bc2) + eps))
-// The host passes the step-dependent scalars computed in double precision exactly as torch does.
+// The host passes the step-dependent scalars computed in double precision exactly as torch does.  Every operation below is
+// the correctly rounded IEEE one and subnormals are kept, so the kernel equals a numpy float32 restatement of these lines bit
+// for bit (tests/optim_ref.py:step32), on the float4 path, the tail and the scalar path alike.
 #include <math.h>
 
 #include "t2h_common.h"
@@ -35,7 +37,9 @@ __device__ inline void adam_one(float &p, float g, float &m, float &v, const Ada
     p = __fmul_rn(p, s.decay);
     m = __fadd_rn(m, __fmul_rn(s.one_minus_beta1, __fsub_rn(g, m)));
     v = __fadd_rn(__fmul_rn(v, s.beta2), __fmul_rn(__fmul_rn(s.one_minus_beta2, g), g));
-    float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(v), s.bc2_sqrt), s.eps);
+    // sqrtf, not __fsqrt_rn: HIP's __fsqrt_rn is the NATIVE square root (v_sqrt_f32, 1 ulp), sqrtf the correctly rounded one
+    // (tests/test_hip_optim.py holds this function to a numpy float32 restatement bit for bit)
+    float denom = __fadd_rn(__fdiv_rn(sqrtf(v), s.bc2_sqrt), s.eps);
     p = __fadd_rn(p, __fmul_rn(s.neg_step_size, __fdiv_rn(m, denom)));
 }
 
