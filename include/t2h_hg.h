@@ -1,0 +1,62 @@
+/* t2h_hg.h -- C ABI of the hourglass image encoder's own kernels in libt2h_hip.so (csrc/hourglass.hip): GroupNorm statistics
+ * and apply, the direct stride-2 convolution, the 2 x 2 average pool and the ConvBlock tail -- what the reference's
+ * tomosar2height/encoder/hourglass.py (ConvBlock :25-82, HourGlass :85-131, HGFilter :134-218) needs beside the 3 x 3 / 1 x 1
+ * convolutions and the bicubic upsampling of t2h.h.  Forward only: the encoder built on them runs for inference (DESIGN.md
+ * section 4.10).
+ *
+ * Same conventions as t2h.h: device pointers owned by the caller, no allocation, no state, stream-ordered calls, 0 or a
+ * negative T2H_ERR_* code, every argument validated before any launch.  The entries live in the same library but are typed by
+ * tomosar2height_amd/encoder/hourglass.py (its own SIGNATURES table); T2H_ABI_VERSION is unchanged.
+ *
+ * Every tensor is dense fp32 NHWC ([B, H, W, C]); pointers are 16-byte aligned and, except for the convolution's input, C is a
+ * multiple of 4 (16-byte loads and stores along C).  No kernel uses a float atomic, waits for another workgroup or depends on
+ * scheduling: two runs give the same bytes.
+ */
+#ifndef T2H_HG_H_
+#define T2H_HG_H_
+
+#include "t2h.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* Bytes t2h_hg_groupnorm_stats needs for the shape (the per-workgroup partials of groups that span several workgroups; 1 byte
+ * is reported when one workgroup covers a sample, so that the caller always has a buffer).  0 for arguments the entry refuses. */
+size_t t2h_hg_groupnorm_workspace_bytes(int B, int H, int W, int C, int G);
+
+/* GroupNorm(G, C) statistics of x [B, H, W, C]: stats [B, G, 2] = (mean, rstd) per sample and group, rstd = 1 / sqrt(var + eps)
+ * with the biased variance over the H * W * C / G elements of the group.  x is read once: every thread keeps a running
+ * (n, mean, M2) per channel (Welford), and the partials are merged pairwise (n, mean, M2) -> (n, mean, M2) in a fixed order --
+ * within a workgroup through LDS, across the workgroups of a sample through `workspace` in a second launch; the variance is
+ * never formed as E[x^2] - E[x]^2.  C % 4 == 0, C % G == 0, at most 2^24 elements per group. */
+int t2h_hg_groupnorm_stats(const float *x, int B, int H, int W, int C, int G, float eps, float *stats, void *workspace,
+                           size_t workspace_bytes, t2h_stream_t stream);
+
+/* y = relu?(((x - mean) * rstd) * scale[c] + shift[c]) with (mean, rstd) = stats[b, c / (C / G)] -- GroupNorm's affine output --
+ * or, stats == NULL (G ignored), y = relu?(x * scale[c] + shift[c]): BatchNorm in eval() with the running statistics folded
+ * into scale and shift by the caller.  Every operation is rounded once in fp32 (no fused multiply-add); relu is max(., 0).
+ * y must not overlap x. */
+int t2h_hg_norm_apply(const float *x, const float *stats, const float *scale, const float *shift, int B, int H, int W, int C, int G,
+                      int relu, float *y, t2h_stream_t stream);
+
+/* Direct K x K convolution with stride 2 and zero padding `pad`: x [B, H, W, Cin] -> y [B, OH, OW, Cout], OH = (H + 2 pad - K) / 2
+ * + 1 (OW likewise), y = bias + sum over (cin chunk, ky) of [sum over (kx, ci) of x * w]: the inner sums by fp32 fused
+ * multiply-adds in that order, each added to the running sum in (chunk, ky) order.  `w` is [K][K][Cin][Cout] (Cout contiguous); bias [Cout] or NULL.  K odd, 1 <= K <= 7, Cout a multiple of 64, any
+ * Cin >= 1 (x needs 4-byte alignment only).  One workgroup per 8 x 8 output tile and 64 output channels, weights and the input
+ * patch in LDS. */
+int t2h_hg_conv_s2_fwd(const float *x, const float *w, const float *bias, float *y, int B, int H, int W, int Cin, int Cout, int K,
+                       int pad, t2h_stream_t stream);
+
+/* 2 x 2 average pool, stride 2: y [B, H / 2, W / 2, C] = (((x00 + x01) + x10) + x11) * 0.25 (row-major order of the window). */
+int t2h_hg_avgpool2x2(const float *x, int B, int H, int W, int C, float *y, t2h_stream_t stream);
+
+/* ConvBlock tail: y [P, C] = cat(o1 [P, C / 2], o2 [P, C / 4], o3 [P, C / 4]) + res [P, C] over P pixels in one pass.
+ * C % 16 == 0. */
+int t2h_hg_block_tail(const float *o1, const float *o2, const float *o3, const float *res, int64_t P, int C, float *y,
+                      t2h_stream_t stream);
+
+#ifdef __cplusplus
+}
+#endif
+#endif /* T2H_HG_H_ */

@@ -14,7 +14,7 @@ OUT = os.path.join(os.path.dirname(HERE), "libt2h_hip.so")
 ARCH = "gfx950"
 _INCLUDE = os.path.join(os.path.dirname(os.path.dirname(HERE)), "include")
 PUBLIC_HEADERS = [os.path.join(_INCLUDE, h) for h in ("t2h.h", "t2h_eval.h", "t2h_inst.h", "t2h_interp.h", "t2h_cloud.h",
-                                                       "t2h_tin.h", "t2h_pnpp.h")]
+                                                       "t2h_tin.h", "t2h_pnpp.h", "t2h_hg.h")]
 
 
 def sources():

@@ -1,20 +1,12 @@
-"""Encoder registry with the reference's keys (tomosar2height/encoder/__init__.py:3-8).  ``pointnet_plus_plus`` is built for
-inference (encoder/pointnetpp.py; ``forward`` under ``train()`` raises).  ``hourglass``, which no reference config selects, is
-out of the hot-path scope and raises a clear error instead of silently missing."""
-from . import alto, pointnet, pointnetpp, unet
-
-
-class _NotBuilt:
-    def __init__(self, name):
-        self.name = name
-
-    def __call__(self, *args, **kwargs):
-        raise NotImplementedError(f"encoder '{self.name}' is outside the MI355X hot-path scope (SURVEY.md section 8)")
-
+"""Encoder registry with the reference's keys (tomosar2height/encoder/__init__.py:3-8); every key is built.
+``pointnet_plus_plus`` (encoder/pointnetpp.py) and ``hourglass`` (encoder/hourglass.py, the image encoder ``model.encoder2:
+hourglass`` selects) run for inference only: their forwards raise where training would need a backward that is not built
+(DESIGN.md section 8)."""
+from . import alto, hourglass, pointnet, pointnetpp, unet
 
 encoder_dict = {
     "pointnet_local_pool": pointnet.LocalPoolPointnet,
     "pointnet_plus_plus": pointnetpp.PointNetPlusPlus,
-    "hourglass": _NotBuilt("hourglass"),
+    "hourglass": hourglass.HGFilter,
     "unet": unet.UNet,
 }
