@@ -186,10 +186,3 @@ def model_cfg(g):
                                      num_hourglass=int(g["model_num_hourglass"]))
     cfg.model.decoder_pixel_kwargs.output_size = int(g["output_size"])
     return cfg
-
-
-def declared_symbols(header_path):
-    """The t2h_* functions a C header declares (comments stripped)."""
-    import re
-    text = re.sub(r"/\*.*?\*/", "", open(header_path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(t2h_[a-z0-9_]+)\s*\(", text)))

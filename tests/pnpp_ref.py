@@ -164,13 +164,6 @@ def ref64(g, name, key):
     return g[f"{name}_{key}"].astype(np.float64) + g[f"{name}_{key}_q"].astype(np.float64) * dev, 4.0 * dev
 
 
-def declared_symbols(header_path):
-    """The t2h_* functions a C header declares (comments stripped)."""
-    import re
-    text = re.sub(r"/\*.*?\*/", "", open(header_path).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(t2h_[a-z0-9_]+)\s*\(", text)))
-
-
 def coincident(targets, sources):
     """Rows of ``targets`` [N, 3] whose float64 d2 by differences to the nearest of ``sources`` [S, 3] is below 1e-12."""
     d = targets.astype(np.float64)[:, None, :] - sources.astype(np.float64)[None, :, :]

@@ -6,13 +6,9 @@ import re
 import pytest
 import torch
 
+from abi_ref import declared_symbols
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _declared_symbols():
-    text = open(os.path.join(ROOT, "include", "t2h.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(t2h_[a-z0-9_]+)\s*\(", text)))
 
 
 def test_library_exports_every_declared_symbol():
@@ -20,7 +16,7 @@ def test_library_exports_every_declared_symbol():
     from tomosar2height_amd.csrc import build
     build.build()
     lib = _lib.load()
-    declared = _declared_symbols()
+    declared = declared_symbols("t2h.h")
     assert len(declared) >= 36
     for name in declared:
         assert hasattr(lib, name), f"{name} declared in include/t2h.h but not exported"

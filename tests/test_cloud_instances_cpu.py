@@ -7,7 +7,7 @@ import torch
 
 import cloud_inst_ref
 from conftest import load_golden
-from test_evaluator_cpu import _declared_symbols
+from abi_ref import declared_symbols
 
 THREE = ("RMSE-B", "MAE-B", "MedAE-B")
 CASES = ("north_up", "rotated")
@@ -93,7 +93,7 @@ def test_inverse_coefficients_match_the_stand_in_bit_for_bit():
 def test_cloud_header_matches_signatures_and_library():
     from tomosar2height_amd import _lib, cloud_instances, evaluator, instances, interpolate
     from tomosar2height_amd.csrc import build
-    declared = _declared_symbols("t2h_cloud.h")
+    declared = declared_symbols("t2h_cloud.h")
     assert declared == sorted(cloud_instances.SIGNATURES) and len(declared) == 4
     assert all(name.startswith("t2h_cloud_") for name in declared)
     lib = cloud_instances.load()
@@ -104,7 +104,7 @@ def test_cloud_header_matches_signatures_and_library():
     for name, sig in instances.SIGNATURES.items():           # load() types what the labels and raster medians go through
         assert list(getattr(lib, name).argtypes) == sig[1], name
     for header in ("t2h.h", "t2h_eval.h", "t2h_inst.h", "t2h_interp.h"):
-        assert not any("t2h_cloud" in name for name in _declared_symbols(header))
+        assert not any("t2h_cloud" in name for name in declared_symbols(header))
     others = list(_lib.SIGNATURES) + list(evaluator.SIGNATURES) + list(instances.SIGNATURES) + list(interpolate.SIGNATURES)
     assert not any("t2h_cloud" in name for name in others)
     assert _lib.ABI_VERSION == 19 == lib.t2h_abi_version()

@@ -1,16 +1,12 @@
 """CPU (no GPU needed): the numpy restatement of the DSM evaluation (tests/eval_ref.py) reproduces the fixture made from the
 reference's own DSMEvaluator.eval / dilate_mask, and the boundary of include/t2h_eval.h holds without a device."""
-import os
-import re
-
 import numpy as np
 import pytest
 import torch
 
 import eval_ref
+from abi_ref import declared_symbols
 from conftest import load_golden
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def fixture_stats(g):
@@ -40,15 +36,9 @@ def test_restatement_reproduces_the_reference_fixture():
             assert np.array_equal(eval_ref.dilate(g[plane], k), g[f"{plane}_dilated{k}"]), (plane, k)
 
 
-def _declared_symbols(header):
-    text = open(os.path.join(ROOT, "include", header)).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(t2h_[a-z0-9_]+)\s*\(", text)))
-
-
 def test_eval_header_matches_signatures_and_library():
     from tomosar2height_amd import _lib, evaluator
-    declared = _declared_symbols("t2h_eval.h")
+    declared = declared_symbols("t2h_eval.h")
     assert declared == sorted(evaluator.SIGNATURES) and len(declared) == 6
     assert all(name.startswith("t2h_eval_") for name in declared)
     lib = evaluator.load()
@@ -56,9 +46,9 @@ def test_eval_header_matches_signatures_and_library():
         fn = getattr(lib, name)
         assert (fn.restype, list(fn.argtypes)) == (evaluator.SIGNATURES[name][0], evaluator.SIGNATURES[name][1]), name
     # the pinned header and table stay as they were: nothing of the evaluator in them, same ABI version
-    assert not any("eval" in name for name in _declared_symbols("t2h.h"))
+    assert not any("eval" in name for name in declared_symbols("t2h.h"))
     assert not any(name.startswith("t2h_eval") for name in _lib.SIGNATURES)
-    assert sorted(_lib.SIGNATURES) == _declared_symbols("t2h.h")
+    assert sorted(_lib.SIGNATURES) == declared_symbols("t2h.h")
     assert _lib.ABI_VERSION == 19 == lib.t2h_abi_version()
 
 

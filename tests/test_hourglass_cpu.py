@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import hg_ref
+from abi_ref import declared_symbols
 from conftest import load_golden
 
 CASES = tuple(hg_ref.CASES)
@@ -140,7 +141,7 @@ def test_header_declares_exactly_the_typed_entry_points():
     from tomosar2height_amd.encoder import hourglass
     headers = [h for h in build.PUBLIC_HEADERS if h.endswith("t2h_hg.h")]
     assert len(headers) == 1
-    assert sorted(hourglass.SIGNATURES) == hg_ref.declared_symbols(headers[0])
+    assert sorted(hourglass.SIGNATURES) == declared_symbols(headers[0])
     assert not set(hourglass.SIGNATURES) & (set(_lib.SIGNATURES) | set(pointops.SIGNATURES))
     assert any(s.endswith("hourglass.hip") for s in build.sources())
     lib = hourglass.load()

@@ -6,7 +6,7 @@ import torch
 
 import inst_ref
 from conftest import load_golden
-from test_evaluator_cpu import _declared_symbols
+from abi_ref import declared_symbols
 
 THREE = ("RMSE-B", "MAE-B", "MedAE-B")
 
@@ -67,7 +67,7 @@ def test_restatement_medians_follow_numpy():
 
 def test_inst_header_matches_signatures_and_library():
     from tomosar2height_amd import _lib, evaluator, instances
-    declared = _declared_symbols("t2h_inst.h")
+    declared = declared_symbols("t2h_inst.h")
     assert declared == sorted(instances.SIGNATURES) and len(declared) == 5
     assert all(name.startswith("t2h_inst_") for name in declared)
     lib = instances.load()
@@ -75,7 +75,7 @@ def test_inst_header_matches_signatures_and_library():
         fn = getattr(lib, name)
         assert (fn.restype, list(fn.argtypes)) == (instances.SIGNATURES[name][0], instances.SIGNATURES[name][1]), name
     for header in ("t2h.h", "t2h_eval.h"):
-        assert not any("t2h_inst" in name for name in _declared_symbols(header))
+        assert not any("t2h_inst" in name for name in declared_symbols(header))
     assert not any("t2h_inst" in name for name in list(_lib.SIGNATURES) + list(evaluator.SIGNATURES))
     assert _lib.ABI_VERSION == 19 == lib.t2h_abi_version()
     text = open(_lib.os.path.join(_lib.os.path.dirname(_lib._HERE), "include", "t2h_inst.h")).read()

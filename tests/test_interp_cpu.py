@@ -7,7 +7,7 @@ import torch
 
 import interp_ref
 from conftest import load_golden
-from test_evaluator_cpu import _declared_symbols
+from abi_ref import declared_symbols
 
 CASES = ("main", "coarse", "sparse")
 # largest share of pixels whose k-th and (k + 1)-th neighbours tie (the k-d tree may return either: left out of the
@@ -67,7 +67,7 @@ def test_restatement_tie_rule_and_fixed_order():
 def test_interp_header_matches_signatures_and_library():
     from tomosar2height_amd import _lib, evaluator, instances, interpolate
     from tomosar2height_amd.csrc import build
-    declared = _declared_symbols("t2h_interp.h")
+    declared = declared_symbols("t2h_interp.h")
     assert declared == sorted(interpolate.SIGNATURES) and len(declared) == 8
     assert all(name.startswith("t2h_interp_") for name in declared)
     lib = interpolate.load()
@@ -75,7 +75,7 @@ def test_interp_header_matches_signatures_and_library():
         fn = getattr(lib, name)
         assert (fn.restype, list(fn.argtypes)) == (interpolate.SIGNATURES[name][0], interpolate.SIGNATURES[name][1]), name
     for header in ("t2h.h", "t2h_eval.h", "t2h_inst.h"):
-        assert not any("t2h_interp" in name for name in _declared_symbols(header))
+        assert not any("t2h_interp" in name for name in declared_symbols(header))
     others = list(_lib.SIGNATURES) + list(evaluator.SIGNATURES) + list(instances.SIGNATURES)
     assert not any("t2h_interp" in name for name in others)
     assert _lib.ABI_VERSION == 19 == lib.t2h_abi_version()

@@ -6,6 +6,7 @@ import pytest
 import torch
 
 import pnpp_ref
+from abi_ref import declared_symbols
 from conftest import load_golden
 
 UNAMBIGUOUS = ("n700", "n1536b2", "n300")
@@ -148,7 +149,7 @@ def test_header_declares_exactly_the_typed_entry_points():
     from tomosar2height_amd import _lib, pointops
     from tomosar2height_amd.csrc import build
     header = [h for h in build.PUBLIC_HEADERS if h.endswith("t2h_pnpp.h")][0]
-    assert sorted(pointops.SIGNATURES) == pnpp_ref.declared_symbols(header)
+    assert sorted(pointops.SIGNATURES) == declared_symbols(header)
     assert not set(pointops.SIGNATURES) & set(_lib.SIGNATURES)
     assert any(h.endswith("t2h_pnpp.h") for h in build.PUBLIC_HEADERS)
     assert pointops.FPS_ONE_WG_MAX == 2048 and "#define T2H_FPS_ONE_WG_MAX 2048" in open(

@@ -7,7 +7,7 @@ import torch
 
 import tin_ref
 from conftest import load_golden
-from test_evaluator_cpu import _declared_symbols
+from abi_ref import declared_symbols
 
 CASES = ("tiny", "mid", "fine", "clustered", "strip", "on_node")
 SHAPES = {"tiny": (10, 12), "mid": (40, 48), "fine": (80, 96), "clustered": (64, 64), "strip": (6, 80), "on_node": (40, 48)}
@@ -88,7 +88,7 @@ def test_brute_force_and_barycentric_on_a_known_square():
 def test_tin_header_matches_signatures_and_library():
     from tomosar2height_amd import _lib, cloud_instances, evaluator, instances, interpolate
     from tomosar2height_amd.csrc import build
-    declared = _declared_symbols("t2h_tin.h")
+    declared = declared_symbols("t2h_tin.h")
     assert declared == sorted(interpolate.TIN_SIGNATURES) and len(declared) == 4
     assert all(name.startswith("t2h_tin_") for name in declared)
     lib = interpolate.load()
@@ -97,7 +97,7 @@ def test_tin_header_matches_signatures_and_library():
         sig = interpolate.TIN_SIGNATURES[name]
         assert (fn.restype, list(fn.argtypes)) == (sig[0], sig[1]), name
     for header in ("t2h.h", "t2h_eval.h", "t2h_inst.h", "t2h_interp.h", "t2h_cloud.h"):
-        assert not any("t2h_tin" in name for name in _declared_symbols(header))
+        assert not any("t2h_tin" in name for name in declared_symbols(header))
     others = (list(_lib.SIGNATURES) + list(evaluator.SIGNATURES) + list(instances.SIGNATURES) + list(interpolate.SIGNATURES) +
               list(cloud_instances.SIGNATURES))
     assert not any("t2h_tin" in name for name in others)

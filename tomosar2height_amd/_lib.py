@@ -1,5 +1,11 @@
-"""ctypes binding of libt2h_hip.so (include/t2h.h).  This is the ONLY way the package reaches the
+"""ctypes binding of libt2h_hip.so (include/*.h).  This is the ONLY way the package reaches the
 device: there is no torch/CPU fallback -- a missing library or a non-GPU tensor raises.
+
+One rule for the C ABI: a public header is bound by exactly one ``declare(header, SIGNATURES)``, in the module that wraps it
+(this one for t2h.h), and nothing undeclared can be called.  ``load()`` types every declared entry in one loop; ``call`` and
+``ws_bytes`` resolve declared names only.  Code that calls an entry directly on the handle takes the handle from ``load()`` in
+the same function (``lib = load()``), never from a stored attribute: the handle is handed out only with every declared entry
+typed.  (An untyped ctypes call would pass a 64-bit device pointer as a C int.)
 
 torch is imported first on purpose: it loads its bundled libamdhip64.so.7, and the dynamic linker then
 resolves our DT_NEEDED entry of the same SONAME to that already-loaded runtime, so device pointers,
@@ -274,8 +280,40 @@ def fallback_counts(reset: bool = False) -> dict:
     return out
 
 
+_registry = {}          # header -> its SIGNATURES table, as declared
+_declared = {}          # name -> (restype, argtypes) of every declared entry
+
+
+def _type(lib, signatures):
+    for name, (res, args) in signatures.items():
+        try:
+            fn = getattr(lib, name)
+        except AttributeError as e:
+            raise T2HLibraryError(f"{LIB_PATH} does not export {name}; rebuild it") from e
+        fn.restype, fn.argtypes = res, args
+
+
+def declare(header: str, signatures: dict):
+    """Bind the entry points of one public header: ``signatures`` = name -> (restype, argtypes), one to one with the header.
+    Never loads the library; if it is loaded already, the new entries are typed at once, so import order and load order do not
+    matter (no per-module ``_typed`` flag, no module loading another's table).  A name declared twice raises; the same table
+    for the same header again (a module reload) does nothing."""
+    if header in _registry and _registry[header] == signatures:
+        return
+    twice = [header] if header in _registry else sorted(set(signatures) & set(_declared))
+    if twice:
+        raise T2HLibraryError(f"declare({header!r}): {', '.join(twice)} declared already")
+    if _lib is not None:
+        _type(_lib, signatures)
+    _registry[header] = dict(signatures)
+    _declared.update(signatures)
+
+
+declare("t2h.h", SIGNATURES)
+
+
 def load():
-    """Load (once) and type the library.  Raises T2HLibraryError if it is missing or stale."""
+    """Load (once) the library and type every declared entry.  Raises T2HLibraryError if it is missing or stale."""
     global _lib
     if _lib is not None:
         return _lib
@@ -284,12 +322,7 @@ def load():
             f"{LIB_PATH} not found: build it with `python -m tomosar2height_amd.csrc.build` "
             "(hipcc --offload-arch=gfx950).  There is no fallback path.")
     lib = ctypes.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        try:
-            fn = getattr(lib, name)
-        except AttributeError as e:
-            raise T2HLibraryError(f"{LIB_PATH} does not export {name}; rebuild it") from e
-        fn.restype, fn.argtypes = res, args
+    _type(lib, _declared)
     if lib.t2h_abi_version() != ABI_VERSION:
         raise T2HLibraryError(f"ABI version mismatch: library {lib.t2h_abi_version()}, binding {ABI_VERSION}")
     _lib = lib
@@ -342,6 +375,14 @@ def timing() -> bool:
 _fn_cache = {}
 
 
+def _entry(name: str):
+    """The typed entry point ``name``: only a declared name resolves."""
+    if name not in _declared:
+        raise T2HLibraryError(f"{name} is not declared: the module that binds its header (`_lib.declare`) has not been imported, "
+                              "and an untyped call would truncate 64-bit device pointers")
+    return getattr(load(), name)
+
+
 # test instrumentation: NaN patterns into every free CU's LDS before every entry point (t2h_debug_poison_lds, include/t2h.h)
 _POISON_LDS = os.environ.get("T2H_POISON_LDS", "0") == "1"
 
@@ -352,7 +393,7 @@ def call(name: str, *args, nbytes: int = 0, flops: int = 0, tag: str = None):
     KernelTimeline is active."""
     fn = _fn_cache.get(name)
     if fn is None:
-        fn = _fn_cache[name] = getattr(load(), name)
+        fn = _fn_cache[name] = _entry(name)
     if _POISON_LDS:
         load().t2h_debug_poison_lds(stream())
     tl = _timeline
@@ -388,7 +429,7 @@ def ws_bytes(name: str, *args) -> int:
     key = (name, args)
     hit = _ws_cache.get(key)
     if hit is None:
-        hit = _ws_cache[key] = int(getattr(load(), name)(*args))
+        hit = _ws_cache[key] = int(_entry(name)(*args))
     return hit
 
 
@@ -474,6 +515,27 @@ class Ready:
         if not torch.cuda.is_current_stream_capturing():       # (a capture is preceded by warm-up passes and a device-wide wait)
             torch.cuda.current_stream().wait_event(self.event)
         self.seen.add(cur)
+
+
+class Derived:
+    """Device tensors derived from parameters (a re-laid weight, a folded BatchNorm), cached per version of every source tensor;
+    the entry carries the event behind its fill (``Ready``)."""
+
+    def __init__(self):
+        self.entries = {}
+
+    def get(self, key, sources, make):
+        version = tuple((t.data_ptr(), t._version) for t in sources)
+        hit = self.entries.get(key)
+        if hit is not None and hit[0] == version:
+            hit[2].wait()
+            return hit[1]
+        with torch.no_grad():
+            value = make()
+        ready = Ready()
+        ready.mark()
+        self.entries[key] = (version, value, ready)
+        return value
 
 
 def require_device(*tensors, what="t2h op"):

@@ -10,7 +10,7 @@ points has a NaN height: ``"valid_only"`` drops it, ``"all"`` counts it as heigh
 per building (lines 193-199, exact on 64-bit keys), ``CloudBuildingEvaluator.eval`` the rest.  Labels and the float32 medians of
 the DTM and nDSM planes come from ``instances`` (csrc/dsm_instances.hip).
 
-The entry points are declared in include/t2h_cloud.h and typed here (``SIGNATURES``), not in ``_lib.SIGNATURES``.
+The entry points of include/t2h_cloud.h are bound here: ``_lib.declare("t2h_cloud.h", SIGNATURES)``.
 """
 import ctypes
 import math
@@ -41,23 +41,8 @@ LAUNCHES_PER_ASSIGN = 2                 # the clear of n_bad, the kernel
 LAUNCHES_PER_MEDIANS = 2 + 1 + 3 + 1 + 2 + 8 * 2
 LAUNCHES_PER_EVAL = LAUNCHES_PER_ASSIGN + LAUNCHES_PER_MEDIANS + 1
 
-_typed = False
-
-
-def load():
-    """The library handle with the t2h_cloud_* entries typed (untyped ctypes calls would truncate 64-bit pointers)."""
-    global _typed
-    lib = _lib.load()
-    if not _typed:
-        instances.load()                # labels and the raster medians go through t2h_inst_* (and t2h_eval_predicate)
-        for name, (res, args) in SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise _lib.T2HLibraryError(f"{_lib.LIB_PATH} does not export {name}; rebuild it") from e
-            fn.restype, fn.argtypes = res, args
-        _typed = True
-    return lib
+_lib.declare("t2h_cloud.h", SIGNATURES)
+load = _lib.load
 
 
 def inverse_coefficients(transform):
@@ -123,7 +108,6 @@ def assign_points(points: torch.Tensor, labels: torch.Tensor, transform):
     ``transform`` the FORWARD six coefficients ``(a, b, c, d, e, f)`` as rasterio / affine give them.  A point outside the raster
     takes the nearest border pixel's label (the reference's clip).  A point whose x or y is not finite raises ``ValueError``
     (one 4-byte copy): the reference's ``astype(int)`` of a NaN is platform-defined."""
-    load()
     inverse = inverse_coefficients(transform)
     points = _cloud(points, "assign_points", 2)
     _plane(labels, "assign_points labels")
@@ -142,7 +126,6 @@ def point_medians(z_or_points: torch.Tensor, point_label: torch.Tensor, K: int):
     """``(counts int32 [K], medians float64 [K])`` on the device: ``np.median(z[point_label == k])`` for k = 1..K, exact in
     float64; NaN (and count 0) for a building without points, NaN for one with a NaN z.  ``z_or_points``: float64 [N] (any
     stride) or [N, >= 3] points, whose column 2 is z."""
-    load()
     if not isinstance(z_or_points, torch.Tensor) or z_or_points.dim() == 2:
         pts = _cloud(z_or_points, "point_medians", 3)
         N, stride, z_ptr = pts.shape[0], _row_stride(pts), _lib.ptr(pts) + 16
@@ -185,7 +168,6 @@ class CloudBuildingEvaluator:
         ``transform`` = the forward six coefficients of that grid (pixel -> world).  The reference crops its rasters by a row or
         two before it uses them and keeps the uncropped file's transform; pass the planes as they are used, with the transform
         they are used with."""
-        load()
         self.inverse = inverse_coefficients(transform)
         self.transform = tuple(float(v) for v in tuple(transform)[:6])
         _plane(building_mask, "CloudBuildingEvaluator building_mask")

@@ -10,7 +10,7 @@ Constructor signatures, defaults, attribute names and ``state_dict`` keys and sh
 Every layer runs on a t2h kernel over channels_last planes: the unbiased 3 x 3 convolutions on ``grid.conv3x3_fwd_``, every 1 x 1
 convolution on ``grid.conv1x1`` (``previous + ll + tmp_out_`` rides its addend epilogue), ``up1 + up2`` on the bicubic kernel's
 addend, and GroupNorm / folded BatchNorm, the stride-2 convolutions, the average pool and ``cat(out1, out2, out3) + residual``
-on csrc/hourglass.hip (include/t2h_hg.h, typed here in ``SIGNATURES``).  ``bn1`` and ``bn4`` of a ConvBlock normalise the same
+on csrc/hourglass.hip (include/t2h_hg.h, bound here: ``_lib.declare``).  ``bn1`` and ``bn4`` of a ConvBlock normalise the same
 tensor with the same groups: one statistics pass serves both.  The kernels have no NCHW form: an NCHW input is converted at the
 module boundary, whatever ``TomoSAR2Height.set_channels_last`` says, and the output is channels_last memory.
 
@@ -38,22 +38,8 @@ SIGNATURES = {
     "t2h_hg_block_tail": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _vp]),
 }
 
-_typed = False
-
-
-def load():
-    """The library handle with the hourglass entries typed (untyped ctypes calls would truncate 64-bit pointers)."""
-    global _typed
-    lib = _lib.load()
-    if not _typed:
-        for name, (res, args) in SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise _lib.T2HLibraryError(f"{_lib.LIB_PATH} does not export {name}; rebuild it") from e
-            fn.restype, fn.argtypes = res, args
-        _typed = True
-    return lib
+_lib.declare("t2h_hg.h", SIGNATURES)
+load = _lib.load
 
 
 # ------------------------------------------------------------------------------------------------ kernels
@@ -70,7 +56,6 @@ def _plane(x: torch.Tensor, what: str) -> torch.Tensor:
 
 def group_norm_stats(x: torch.Tensor, groups: int, eps: float) -> torch.Tensor:
     """[B, G, 2] = (mean, rstd) of GroupNorm(groups, C) over the channels_last plane ``x``."""
-    load()
     b, c, h, w = x.shape
     stats = torch.empty(b, groups, 2, dtype=torch.float32, device=x.device)
     nws = _lib.ws_bytes("t2h_hg_groupnorm_workspace_bytes", b, h, w, c, groups)
@@ -84,7 +69,6 @@ def group_norm_stats(x: torch.Tensor, groups: int, eps: float) -> torch.Tensor:
 
 def norm_apply(x: torch.Tensor, stats, scale: torch.Tensor, shift: torch.Tensor, groups: int, relu: bool) -> torch.Tensor:
     """relu?(((x - mean) * rstd) * scale + shift) with ``stats`` of ``group_norm_stats``, or relu?(x * scale + shift) without."""
-    load()
     b, c, h, w = x.shape
     y = grid._empty_cl(b, c, h, w, x.device)
     _lib.call("t2h_hg_norm_apply", _lib.ptr(x), _lib.ptr(stats) if stats is not None else None, _lib.ptr(scale), _lib.ptr(shift),
@@ -94,7 +78,6 @@ def norm_apply(x: torch.Tensor, stats, scale: torch.Tensor, shift: torch.Tensor,
 
 def conv_s2(x: torch.Tensor, w_kkio: torch.Tensor, bias, k: int, pad: int) -> torch.Tensor:
     """K x K / stride 2 / zero padding ``pad`` of the channels_last plane ``x``; ``w_kkio``: the weight as [K, K, Cin, Cout]."""
-    load()
     b, cin, h, w = x.shape
     cout = w_kkio.shape[3]
     oh, ow = (h + 2 * pad - k) // 2 + 1, (w + 2 * pad - k) // 2 + 1
@@ -106,7 +89,6 @@ def conv_s2(x: torch.Tensor, w_kkio: torch.Tensor, bias, k: int, pad: int) -> to
 
 
 def avgpool2x2(x: torch.Tensor) -> torch.Tensor:
-    load()
     b, c, h, w = x.shape
     y = grid._empty_cl(b, c, h // 2, w // 2, x.device)
     _lib.call("t2h_hg_avgpool2x2", _lib.ptr(x), b, h, w, c, _lib.ptr(y), _lib.stream(), nbytes=4 * (x.numel() + y.numel()))
@@ -115,7 +97,6 @@ def avgpool2x2(x: torch.Tensor) -> torch.Tensor:
 
 def block_tail(o1, o2, o3, res) -> torch.Tensor:
     """cat(o1, o2, o3, dim=1) + res in one pass."""
-    load()
     b, c, h, w = res.shape
     if (o1.shape[1], o2.shape[1], o3.shape[1]) != (c // 2, c // 4, c // 4):
         raise ValueError("block_tail: inputs of C / 2, C / 4 and C / 4 channels expected")
@@ -135,10 +116,6 @@ def upsample2x_bicubic_add(x: torch.Tensor, addend: torch.Tensor) -> torch.Tenso
 
 
 # ------------------------------------------------------------------------------------------------ module plumbing
-def _pow2(v: int) -> bool:
-    return v > 0 and (v & (v - 1)) == 0
-
-
 def _require_inference(module: nn.Module, what: str):
     if torch.is_grad_enabled() and any(p.requires_grad for p in module.parameters()):
         raise NotImplementedError(f"{what} runs for inference only (call it under torch.no_grad()): the backward of GroupNorm, of the "
@@ -149,37 +126,16 @@ def _require_inference(module: nn.Module, what: str):
 
 def _check_planes(x, what, min_h, min_w):
     h, w = x.shape[2], x.shape[3]
-    if not (_pow2(h) and _pow2(w) and h >= min_h and w >= min_w):
+    if not (grid._pow2(h) and grid._pow2(w) and h >= min_h and w >= min_w):
         raise ValueError(f"{what}: H={h}, W={w} must be powers of two, at least {min_h} x {min_w} (the 3 x 3 convolution kernels "
                          "take power-of-two planes)")
 
 
-class _Derived:
-    """Device tensors derived from parameters (a re-laid weight, a folded BatchNorm), cached per version of every source tensor;
-    the entry carries the event behind its fill (``_lib.Ready``)."""
-
-    def __init__(self):
-        self.entries = {}
-
-    def get(self, key, sources, make):
-        version = tuple((t.data_ptr(), t._version) for t in sources)
-        hit = self.entries.get(key)
-        if hit is not None and hit[0] == version:
-            hit[2].wait()
-            return hit[1]
-        with torch.no_grad():
-            value = make()
-        ready = _lib.Ready()
-        ready.mark()
-        self.entries[key] = (version, value, ready)
-        return value
-
-
 class _HGModule(nn.Module):
-    def _derived(self) -> _Derived:
+    def _derived(self) -> _lib.Derived:
         d = self.__dict__.get("_hg_derived")
         if d is None:
-            d = self.__dict__["_hg_derived"] = _Derived()
+            d = self.__dict__["_hg_derived"] = _lib.Derived()
         return d
 
     def _norm(self, x, name, relu, stats=None):

@@ -34,7 +34,7 @@ class _FoldedLayers(nn.Module):
     """``mlp_convs`` / ``mlp_bns`` of one stage and their folded form: W' = W * s, b' = (b - mean) * s + beta with
     s = gamma / sqrt(var + eps), computed in float64 and rounded once; the first layer's W' is padded with zero columns to the
     row length of its input (a multiple of 4: 16-byte rows for the product kernels; K = 131 and 259 have no kernel otherwise).
-    Cached per version of every tensor involved; the cache entry carries the event behind its fill (``_lib.Ready``)."""
+    Cached per version of every tensor involved (``_lib.Derived``)."""
 
     def _make_layers(self, conv, bn, in_channel, widths):
         self.mlp_convs = nn.ModuleList()
@@ -44,34 +44,25 @@ class _FoldedLayers(nn.Module):
             self.mlp_convs.append(conv(last, out, 1))
             self.mlp_bns.append(bn(out))
             last = out
-        self.__dict__["_fold"] = None
-
-    def _fold_key(self):
-        key = []
-        for conv, bn in zip(self.mlp_convs, self.mlp_bns):
-            for t in (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var):
-                key.append((t.data_ptr(), t._version))
-        return tuple(key)
+        self.__dict__["_fold"] = _lib.Derived()
 
     def folded(self):
-        key = self._fold_key()
-        hit = self.__dict__.get("_fold")
-        if hit is not None and hit[0] == key:
-            hit[2].wait()
-            return hit[1]
-        layers = []
-        for conv, bn in zip(self.mlp_convs, self.mlp_bns):
-            _lib.require_device(conv.weight, what="PointNetPlusPlus layer")
-            s = bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps)
-            w = conv.weight.reshape(conv.weight.shape[0], -1).double() * s[:, None]
-            b = (conv.bias.double() - bn.running_mean.double()) * s + bn.bias.double()
-            wp = torch.zeros(w.shape[0], _pad4(w.shape[1]), dtype=torch.float32, device=w.device)
-            wp[:, :w.shape[1]] = w
-            layers.append((wp, b.float().contiguous()))
-        ready = _lib.Ready()
-        ready.mark()
-        self.__dict__["_fold"] = (key, layers, ready)
-        return layers
+        pairs = list(zip(self.mlp_convs, self.mlp_bns))
+
+        def fold():
+            layers = []
+            for conv, bn in pairs:
+                _lib.require_device(conv.weight, what="PointNetPlusPlus layer")
+                s = bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps)
+                w = conv.weight.reshape(conv.weight.shape[0], -1).double() * s[:, None]
+                b = (conv.bias.double() - bn.running_mean.double()) * s + bn.bias.double()
+                wp = torch.zeros(w.shape[0], _pad4(w.shape[1]), dtype=torch.float32, device=w.device)
+                wp[:, :w.shape[1]] = w
+                layers.append((wp, b.float().contiguous()))
+            return layers
+
+        sources = [t for conv, bn in pairs for t in (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)]
+        return self.__dict__["_fold"].get("layers", sources, fold)
 
     def _chain(self, rows):
         """relu(bn(conv(.))) of every layer over [M, K] rows."""

@@ -7,7 +7,7 @@ its rasters from GeoTIFF paths; here they are device tensors and the ground trut
 ``DSMGenerator`` takes its own: left / top bound and pixel size, i.e. ``Affine(px, 0, left, 0, -py, top)``.  The reference's
 ``print_statistics`` accepts the returned ``stats`` unchanged.
 
-The entry points are declared in include/t2h_eval.h and typed here (``SIGNATURES``), not in ``_lib.SIGNATURES``.
+The entry points of include/t2h_eval.h are bound here: ``_lib.declare("t2h_eval.h", SIGNATURES)``.
 """
 import ctypes
 import math
@@ -37,22 +37,8 @@ STAT_KEYS = ("max", "min", "MAE", "RMSE", "abs_median", "median", "n_pixel", "NM
 # two median kernels
 LAUNCHES_PER_EVAL = 1 + 1 + 2 + 2 * (8 * 2 + 1)
 
-_typed = False
-
-
-def load():
-    """The library handle with the t2h_eval_* entries typed (untyped ctypes calls would truncate 64-bit pointers)."""
-    global _typed
-    lib = _lib.load()
-    if not _typed:
-        for name, (res, args) in SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise _lib.T2HLibraryError(f"{_lib.LIB_PATH} does not export {name}; rebuild it") from e
-            fn.restype, fn.argtypes = res, args
-        _typed = True
-    return lib
+_lib.declare("t2h_eval.h", SIGNATURES)
+load = _lib.load
 
 
 def _plane(t, what):
@@ -87,7 +73,6 @@ def _dilate(m8, iterations):
 def dilate_mask(mask: torch.Tensor, iterations: int = 1) -> torch.Tensor:
     """utils/dilate_mask.py: ``scipy.ndimage.binary_dilation(mask, iterations=iterations)`` with scipy's defaults (cross
     structuring element, border value 0) on a device bool plane; returns a device bool plane."""
-    load()
     _plane(mask, "dilate_mask")
     m8 = mask.view(torch.uint8) if mask.dtype == torch.bool else _predicate(mask, NONZERO, 0, "dilate_mask")
     return _dilate(m8, iterations).view(torch.bool)
@@ -99,7 +84,6 @@ class DSMEvaluator:
         (px, py); ``gt_mask`` bool / uint8 [R, C] (default: all true); ``other_masks``: dict of [R, C] planes with the
         reference's keys -- ``'building'`` (dilated twice, adds ``'terrain'``), ``'type'`` (values 0 / 1 / 2: adds
         ``non_building, residential, non_residential, building_combined``), any other key used as a bool mask."""
-        load()
         self.gt_dsm = _plane(gt_dsm, "DSMEvaluator gt_dsm")
         if gt_dsm.dtype not in (torch.float32, torch.float64):
             raise TypeError(f"DSMEvaluator: gt_dsm must be float32 or float64, got {gt_dsm.dtype}")

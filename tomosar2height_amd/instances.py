@@ -7,7 +7,7 @@ of every building in the prediction and in the ground truth, then the error over
 the same script (evaluator_instance.py:139-291) are ``cloud_instances.py``; ``segment_medians`` takes any plane of values with a
 plane of labels, and gives them their DTM and nDSM medians.
 
-The entry points are declared in include/t2h_inst.h and typed here (``SIGNATURES``), not in ``_lib.SIGNATURES``.
+The entry points of include/t2h_inst.h are bound here: ``_lib.declare("t2h_inst.h", SIGNATURES)``.
 """
 import ctypes
 import math
@@ -16,7 +16,6 @@ import torch
 
 from . import _lib
 from .evaluator import NONZERO, _plane, _predicate
-from .evaluator import load as _load_evaluator
 
 _vp, _i, _i64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t
 
@@ -40,23 +39,8 @@ LAUNCHES_PER_LABEL = 6
 LAUNCHES_PER_MEDIANS = 2 + 1 + 3 + 1 + 2 + 4 * 2
 LAUNCHES_PER_EVAL = LAUNCHES_PER_MEDIANS + 1
 
-_typed = False
-
-
-def load():
-    """The library handle with the t2h_inst_* entries typed (untyped ctypes calls would truncate 64-bit pointers)."""
-    global _typed
-    lib = _lib.load()
-    if not _typed:
-        _load_evaluator()               # a mask that is not bool / uint8 goes through t2h_eval_predicate (_mask8)
-        for name, (res, args) in SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise _lib.T2HLibraryError(f"{_lib.LIB_PATH} does not export {name}; rebuild it") from e
-            fn.restype, fn.argtypes = res, args
-        _typed = True
-    return lib
+_lib.declare("t2h_inst.h", SIGNATURES)
+load = _lib.load
 
 
 def _mask8(mask, what):
@@ -84,7 +68,6 @@ def label_components(mask: torch.Tensor, connectivity: int = 2):
     """``(labels, K)``: int32 [R, C] device plane with 0 for background and 1..K in raster order of each component's first
     pixel (skimage's and scipy's numbering), and K as a Python int (one 4-byte copy).  ``mask``: any dtype ``DSMEvaluator``
     takes for a mask; nonzero is foreground."""
-    load()
     m8 = _mask8(mask, "label_components")
     labels, k_dev = _label(m8, 0, 0, m8.shape[0], m8.shape[1], connectivity)
     return labels, int(k_dev.item())
@@ -93,7 +76,6 @@ def label_components(mask: torch.Tensor, connectivity: int = 2):
 def segment_medians(values: torch.Tensor, labels: torch.Tensor, K: int, window=None):
     """``(counts int32 [K], medians float32 [K])`` on the device: ``np.median(values32[labels == k])`` for k = 1..K, where
     ``values32`` is ``values`` (float32, or float64 rounded to float32), or its window ``(t_row, l_col)`` of the labels' shape."""
-    load()
     _plane(values, "segment_medians values")
     _plane(labels, "segment_medians labels")
     if values.dtype not in (torch.float32, torch.float64) or labels.dtype != torch.int32:
@@ -123,7 +105,6 @@ class BuildingEvaluator:
     def __init__(self, building_mask, gt_dsm, bounds, pixel_size=(1.0, 1.0), connectivity=2):
         """``building_mask`` [R, C] (nonzero = footprint), ``gt_dsm`` [R, C] float32 / float64, ``bounds`` = (left, top) of
         both rasters, ``pixel_size`` = (px, py): the georeference as ``DSMEvaluator`` takes it."""
-        load()
         self.gt_dsm = _plane(gt_dsm, "BuildingEvaluator gt_dsm")
         if gt_dsm.dtype not in (torch.float32, torch.float64):
             raise TypeError(f"BuildingEvaluator: gt_dsm must be float32 or float64, got {gt_dsm.dtype}")

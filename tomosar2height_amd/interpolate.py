@@ -16,8 +16,8 @@ barycentric coordinates.  No triangulation is built: a node's triangle is found 
 (Qhull drops the points its lifted paraboloid cannot resolve); that is not reproduced, and is why ``linear_dsm`` -- the name
 for the script's own output -- stays unbuilt.
 
-The entry points are declared in include/t2h_interp.h and include/t2h_tin.h and typed here (``SIGNATURES``,
-``TIN_SIGNATURES``), not in ``_lib.SIGNATURES``.
+The entry points of include/t2h_interp.h and include/t2h_tin.h are bound here, one ``_lib.declare`` per header
+(``SIGNATURES``, ``TIN_SIGNATURES``).
 """
 import ctypes
 import math
@@ -66,22 +66,9 @@ TIN_STATUS_COLS = 8     # T2H_TIN_STATUS_COLS
 LAUNCHES_PER_HULL = 4                   # partial extremes, polygon, filter, sort + chain
 LAUNCHES_PER_TIN_RASTER = 1 + 1         # the clear of the status, the search
 
-_typed = False
-
-
-def load():
-    """The library handle with the t2h_interp_* and t2h_tin_* entries typed (untyped ctypes calls would truncate 64-bit pointers)."""
-    global _typed
-    lib = _lib.load()
-    if not _typed:
-        for name, (res, args) in {**SIGNATURES, **TIN_SIGNATURES}.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise _lib.T2HLibraryError(f"{_lib.LIB_PATH} does not export {name}; rebuild it") from e
-            fn.restype, fn.argtypes = res, args
-        _typed = True
-    return lib
+_lib.declare("t2h_interp.h", SIGNATURES)
+_lib.declare("t2h_tin.h", TIN_SIGNATURES)
+load = _lib.load
 
 
 class CloudIndex:
@@ -92,7 +79,6 @@ class CloudIndex:
     costs one 128-byte copy to the host (and the wait for it): the raster's shape depends on what it carries."""
 
     def __init__(self, points: torch.Tensor):
-        load()
         if not isinstance(points, torch.Tensor):
             raise TypeError(f"CloudIndex: expected a torch tensor, got {type(points).__name__}")
         if points.dtype not in (torch.float32, torch.float64):
@@ -190,7 +176,6 @@ def _work(index, ny, nx):
 def grid_knn(index: CloudIndex, resolution: float = 1.0, k: int = 8):
     """``(d2 [ny, nx, k] float64, idx [ny, nx, k] int32)``: squared distances and rows of ``index.unique`` of the k nearest
     neighbours of every raster node, in (d2, X, Y) order."""
-    load()
     if not isinstance(index, CloudIndex):
         raise TypeError(f"grid_knn: expected a CloudIndex, got {type(index).__name__}")
     k = _check_k(index, k, "grid_knn")
@@ -206,7 +191,6 @@ def grid_knn(index: CloudIndex, resolution: float = 1.0, k: int = 8):
 
 def nearest_dsm(points_or_index, resolution: float = 1.0):
     """``(dsm [ny, nx] float64, (xmin, ymin))``: scripts/interpolate_nearest.py on the device."""
-    load()
     index = _index(points_or_index)
     _check_k(index, 1, "nearest_dsm")
     res = _resolution(resolution)
@@ -221,7 +205,6 @@ def nearest_dsm(points_or_index, resolution: float = 1.0):
 def idw_dsm(points_or_index, resolution: float = 1.0, k: int = 8, power: float = 2):
     """``(dsm [ny, nx] float64, (xmin, ymin))``: scripts/interpolate_idw.py on the device.  A coincident point has weight 1
     beside the others' 1 / d^2, as there."""
-    load()
     if power != 2:
         raise ValueError(f"idw_dsm: power = {power!r}; only the reference's power = 2 is built")
     index = _index(points_or_index)
@@ -251,7 +234,6 @@ def grid_simplex(index: CloudIndex, resolution: float = 1.0, return_status: bool
     -1 / NaN outside the convex hull.  The counterpart of ``grid_knn``.  With ``return_status`` a third value: ``{"capped":
     nodes that stopped at 64 pivots, "unresolved": ..., "pivots": ..., "walk_pivots": ...}``; without it, nodes that were capped
     raise a ``RuntimeWarning``."""
-    load()
     if not isinstance(index, CloudIndex):
         raise TypeError(f"grid_simplex: expected a CloudIndex, got {type(index).__name__}")
     res = _resolution(resolution)
@@ -272,7 +254,6 @@ def delaunay_dsm(points_or_index, resolution: float = 1.0, return_status: bool =
     its (xmin, ymin) -- ``griddata(method='linear')`` there -- NaN outside the convex hull.  On raw world coordinates the
     script's Qhull drops points, which is not reproduced.  A cloud without area raises ``ValueError``.
     ``return_status`` as for ``grid_simplex``."""
-    load()
     index = _index(points_or_index)
     res = _resolution(resolution)
     hull = index.hull()

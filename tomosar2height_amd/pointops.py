@@ -10,7 +10,7 @@ differently within a few ulps of 6 at unit coordinates, which can move a point t
 reorder two neighbours that close to equidistant.  Ties are broken by the lowest index everywhere (FPS maxima, 3-NN distances);
 the reference leaves them to ``torch.max`` / an unstable ``sort``.
 
-The entry points are declared in include/t2h_pnpp.h and typed here (``SIGNATURES``), not in ``_lib.SIGNATURES``.
+The entry points of include/t2h_pnpp.h are bound here: ``_lib.declare("t2h_pnpp.h", SIGNATURES)``.
 """
 import ctypes
 import numbers
@@ -38,22 +38,8 @@ FPS_ONE_WG_MAX = 2048       # T2H_FPS_ONE_WG_MAX
 # form with that slice -- how a test runs it on a small cloud.  Both forms give the same bytes.
 FPS_SLICE_DEFAULT = 1024
 
-_typed = False
-
-
-def load():
-    """The library handle with the PointNet++ entries typed (untyped ctypes calls would truncate 64-bit pointers)."""
-    global _typed
-    lib = _lib.load()
-    if not _typed:
-        for name, (res, args) in SIGNATURES.items():
-            try:
-                fn = getattr(lib, name)
-            except AttributeError as e:
-                raise _lib.T2HLibraryError(f"{_lib.LIB_PATH} does not export {name}; rebuild it") from e
-            fn.restype, fn.argtypes = res, args
-        _typed = True
-    return lib
+_lib.declare("t2h_pnpp.h", SIGNATURES)
+load = _lib.load
 
 
 def fps_slice(n: int) -> int:
@@ -123,7 +109,6 @@ def query_ball_point(radius: float, nsample: int, xyz: torch.Tensor, new_xyz: to
     padded with the first.  The threshold is ``radius ** 2`` rounded to fp32."""
     _cloud(xyz, "query_ball_point xyz")
     _cloud(new_xyz, "query_ball_point new_xyz")
-    load()
     b, n, _ = xyz.shape
     s = new_xyz.shape[1]
     idx = torch.empty(b, s, nsample, dtype=torch.long, device=xyz.device)
@@ -135,7 +120,6 @@ def query_ball_point(radius: float, nsample: int, xyz: torch.Tensor, new_xyz: to
 def group_rows(xyz, new_xyz, points, idx, ld=None) -> torch.Tensor:
     """Rows [B * S * nsample, ld] = grouped xyz minus the centroid | grouped features | zeros (``ld`` >= 3 + D: the row length
     the layers' products want, a multiple of 4)."""
-    load()
     b, n, _ = xyz.shape
     _, s, ns = idx.shape
     d = 0 if points is None else points.shape[2]
@@ -165,7 +149,6 @@ def sample_and_group(npoint, radius, nsample, xyz, points, returnfps=False, star
 
 def group_max_rows(rows: torch.Tensor, nsample: int, c: int = None) -> torch.Tensor:
     """[groups * nsample, ld] rows -> [groups, c]: the max over each group's rows (columns 0 .. c)."""
-    load()
     _lib.require_device(rows, what="group_max")
     c = rows.shape[1] if c is None else c
     groups = rows.shape[0] // nsample
@@ -191,7 +174,6 @@ def three_nn_interpolate(xyz1: torch.Tensor, xyz2: torch.Tensor, points2: torch.
     _cloud(xyz1, "three_nn_interpolate xyz1")
     _cloud(xyz2, "three_nn_interpolate xyz2")
     _cloud(points2, "three_nn_interpolate points2", cols=None)
-    load()
     b, n, _ = xyz1.shape
     s, d = xyz2.shape[1], points2.shape[2]
     if points2.shape[:2] != xyz2.shape[:2] or xyz2.shape[0] != b:
