@@ -179,6 +179,23 @@ int t2h_segsum_bwd_multi(const float *const *gplanes_nhwc, const int *levels, co
  *   raster[p, :] = acc[p, :] / max(cnt[p], 1) + [cnt[p] > 0] * cvec[:]                       (alto.py:76-88: count clamped to 1),
  * and its backward (dacc = g / max(cnt, 1); dcvec = sum over non-empty cells of g, two-stage fixed-order column sum;
  * either output may be NULL). */
+/* Compact per-cell matrices (deferred.py, T2H_COMPACT_SUMS).  A row of the per-cell sums of an EMPTY cell is all zeros and the
+ * matching gradient row is never read, so the matrices of the finest deferred resolution hold one row per OCCUPIED cell: rows in
+ * plane order within a tile, tile after tile.  They are allocated at B r r rows (the bound: no host ever reads the count).
+ *
+ * t2h_compact_next(row_of_cell, level, n_rows) is a request for the NEXT launch of the calling thread; the entry point that takes it
+ * clears it, a launch that has no use for it ignores it.  The shapes of the existing calls do not change.
+ *   - t2h_cell_counts with a request for ITS level also writes the level's row list into the caller's int32 buffer
+ *       row_of_cell [P = B r r] (-1: empty cell) | cell_of_row [P] (first n_rows valid) | n_rows, 3 spare | ceil(P / 2048) scratch
+ *     (n_rows must point at row_of_cell + 2 P);
+ *   - t2h_segsum_fwd, t2h_sample_relu_cellsums_ordered (the `sums` output; `level` must be the sums' level) and the fine side of
+ *     t2h_plane_sumpool2x2 address their plane through row_of_cell: an empty cell writes nothing / contributes 0;
+ *   - t2h_segsum_bwd_multi and t2h_sample_bwd_from_sums_ordered read the plane whose level is `level` through row_of_cell;
+ *   - t2h_mean_bias_fwd reads acc[row_of_cell[p]] (an empty cell's output is 0 by a select), t2h_mean_bias_bwd writes
+ *     dacc[row_of_cell[p]]; `cnt`, the output / `g` and the order of the column sums stay per cell;
+ *   - t2h_gemm_bx3 returns from every row tile that starts at or behind *n_rows and stages the rows behind *n_rows of the last tile
+ *     as zeros; t2h_linear_wgrad (fp32 kernel) sums over the first *n_rows rows only.  row_of_cell may be NULL for these. */
+void t2h_compact_next(const int32_t *row_of_cell, int level, const int32_t *n_rows);
 int t2h_cell_counts(const int32_t *off0, int B, int nbits, int level, float *cnt, t2h_stream_t stream);
 int t2h_mean_bias_fwd(const float *acc, const float *cnt, const float *cvec, int64_t P, int C, float *out, t2h_stream_t stream);
 size_t t2h_mean_bias_bwd_workspace_bytes(int64_t P, int C);

@@ -30,6 +30,7 @@ SIGNATURES = {
     "t2h_last_kernel_name": (ctypes.c_char_p, []),
     "t2h_clear_kernel_name": (None, []),
     "t2h_debug_poison_lds": (_i, [_vp]),
+    "t2h_compact_next": (None, [_vp, _i, _vp]),
     "t2h_coordinate2index": (_i, [_vp, _i, _i64, _i, _vp, _vp]),
     "t2h_tile_workspace_bytes": (_sz, [_i, _i, _i]),
     "t2h_tile_build": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -414,6 +415,13 @@ def call(name: str, *args, nbytes: int = 0, flops: int = 0, tag: str = None):
         symbol = lib.t2h_last_kernel_name().decode() or name
         tl.records.append((tag or name, nbytes, flops, s, e, symbol))
     check(rc, name)
+
+
+def compact_next(row_of_cell, level: int, n_rows):
+    """``t2h_compact_next`` (include/t2h.h): the NEXT launch of this thread addresses the per-cell matrix of ALTO level ``level``
+    by occupied row (``row_of_cell``: device pointer or None) and / or stops at ``*n_rows`` rows (device pointer or None).  Call it
+    right before the ``call`` it is meant for: that entry point takes the request and clears it."""
+    load().t2h_compact_next(row_of_cell, level, n_rows)
 
 
 def ptr(t: torch.Tensor) -> int:

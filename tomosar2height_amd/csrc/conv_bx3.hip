@@ -268,6 +268,10 @@ struct RowsArgs {
     // a decoder activation's gradient (pixel.py:31: conv4(cat[x, x1, x2, x3])), formed in this epilogue instead of being written by
     // the head's backward and read back here as "old values" (T2H_ACCUM): same products, same order of additions, same bits
     const float *r1_g, *r1_w;
+    // plain 1-tap (GEMM) form on a compact matrix (t2h_compact_next): device int, the rows in use.  A workgroup whose first row lies
+    // behind them returns; the last partial tile stages the rows behind them as ZEROS (they are uninitialised memory, and a staged
+    // value takes part in the tile's fp16 block scale), and what it computes for them nobody reads
+    const int *row_limit;
 };
 
 // output pixel (2y + dy, 2x + dx) of the transposed convolution for GEMM row m = ((b * H + y) * W + x), tap = 2 dy + dx
@@ -335,6 +339,11 @@ __global__ __launch_bounds__(NT, 2) void bx3_rows_kernel(RowsArgs p) {
     const int x0 = tx * TW, y0 = ty * TH;
     int n0 = tn_lo * BN;
     const int c_beg = split * p.chunks_per_split, c_end = min(p.Kc / CCH, c_beg + p.chunks_per_split);
+    int row_lim = 0x7fffffff;
+    if (NTAP == 1 && UPM == 0 && p.row_limit) {                          // read once per workgroup into an SGPR
+        row_lim = __builtin_amdgcn_readfirstlane(*p.row_limit);
+        if ((b * p.H + y0) * p.W + x0 >= row_lim) return;                // (workgroup-uniform, before any barrier)
+    }
 
     // halo staging: F4 float4 per pixel and chunk
     constexpr int NF4 = HP * F4, PER = (NF4 + NT - 1) / NT;
@@ -352,7 +361,8 @@ __global__ __launch_bounds__(NT, 2) void bx3_rows_kernel(RowsArgs p) {
                 if (idx < NF4)
                     v = *reinterpret_cast<const float4 *>(p.x + up_pixel(((long long)b * p.H + gy) * p.W + gx, tap, p.up_logW, p.up_logH) *
                                                                     p.ldx + co0 + c4 * 4);
-            } else if (idx < NF4 && (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W)
+            } else if (idx < NF4 && (unsigned)gy < (unsigned)p.H && (unsigned)gx < (unsigned)p.W &&
+                       (NTAP != 1 || (b * p.H + gy) * p.W + gx < row_lim))
                 v = *reinterpret_cast<const float4 *>(p.x + (((size_t)b * p.H + gy) * p.W + gx) * p.ldx + c * CCH + c4 * 4);
             hreg[f] = v;
         }
@@ -1257,6 +1267,7 @@ T2H_API size_t t2h_gemm_bx3_workspace_bytes(int64_t M, int K, int N) {
 
 T2H_API int t2h_gemm_bx3(const float *x, int ldx, const void *wf, const float *bias, const float *mask, int ldm, float *y, int ldy,
                          int64_t M, int K, int N, int flags, void *workspace, size_t workspace_bytes, t2h_stream_t stream) {
+    const CompactRows cr = take_compact();
     if (!x || !wf || !y) return fail(T2H_ERR_ARG, "gemm_bx3: null pointer");
     if (!t2h_gemm_bx3_supported(M, K, N))
         return fail(T2H_ERR_ARG, "gemm_bx3: needs M %% 128 == 0, K %% 64 == 0, N %% 32 == 0 (M=%lld K=%d N=%d)", (long long)M, K, N);
@@ -1268,6 +1279,7 @@ T2H_API int t2h_gemm_bx3(const float *x, int ldx, const void *wf, const float *b
     a.B = 1; a.H = (int)(M / 32); a.W = 32; a.Kc = K; a.Nc = N; a.ldx = ldx; a.ldy = ldy; a.ldm = ldm;
     a.flags = ((flags & T2H_RELU_OUT) ? F_RELU_OUT : 0) | ((flags & T2H_ACCUM) ? F_ACCUM : 0);
     a.wscale = f16_trailer(wf, (size_t)K * N * 4);
+    a.row_limit = cr.n_rows;
     return launch_rows(a, npl_of(flags), workspace, workspace_bytes, as_stream(stream), "gemm_bx3", 1);
 }
 

@@ -380,7 +380,7 @@ template <int VEC, bool MEAN = true>
 __global__ __launch_bounds__(kThreads) void segmean_fwd_kernel(const float *__restrict__ feat,
                                                                const int32_t *__restrict__ off0, int B, int nbits,
                                                                int level, int C, int lg, float *__restrict__ plane,
-                                                               int ld_out) {
+                                                               int ld_out, const int32_t *__restrict__ rowmap) {
     int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     int64_t gid = t >> lg;
     const int rbits = nbits - level;
@@ -392,7 +392,12 @@ __global__ __launch_bounds__(kThreads) void segmean_fwd_kernel(const float *__re
     int s = off0[obase], e = off0[obase + ((size_t)1 << (2 * level))];
     int cx = (int)compact1by1(mk), cy = (int)compact1by1(mk >> 1);
     int r = 1 << rbits;
-    float *orow = plane + (((size_t)b * r + cy) * r + cx) * ld_out;     // ld_out >= C: a column block of a wider matrix
+    int64_t orow_i = ((int64_t)b * r + cy) * r + cx;
+    if (rowmap) {                         // compact rows (t2h_compact_next): an empty cell has no row and writes nothing
+        if (e <= s) return;
+        orow_i = rowmap[orow_i];
+    }
+    float *orow = plane + (size_t)orow_i * ld_out;                       // ld_out >= C: a column block of a wider matrix
     float inv_den = (float)(e - s > 0 ? e - s : 1);
     int span = VEC << lg;
     for (int c = ((int)t & ((1 << lg) - 1)) * VEC; c < C; c += span) {
@@ -423,7 +428,24 @@ __global__ __launch_bounds__(kThreads) void segmean_fwd_kernel(const float *__re
 // Gradient of per-cell sums taken at several (<= 8) resolutions of the same rows (t2h_segsum_bwd_multi): one group per point,
 // gfeat[n] = (mask[n] > 0 ?) sum_l gplane_l[cell_l(n)] (+ addend[n]); planes in the order given (a fixed summation order).
 constexpr int kMaxMultiPlanes = 8;
-struct MultiPlanes { const float *g[kMaxMultiPlanes]; int level[kMaxMultiPlanes]; int ld[kMaxMultiPlanes]; int n; };
+struct MultiPlanes {
+    const float *g[kMaxMultiPlanes]; int level[kMaxMultiPlanes]; int ld[kMaxMultiPlanes]; int n;
+    // compact rows (t2h_compact_next): plane `cq` (-1: none) holds one row per OCCUPIED cell, rowmap[cell in plane order] = its row,
+    // -1 for an empty cell; `cells`: entries of rowmap
+    int cq = -1; const int32_t *rowmap = nullptr; int cells = 0;
+};
+// row of plane q that holds cell `ci` (its index in plane order).  q is an unrolled constant and cq a kernel argument: a scalar
+// branch around one more load -- no compare result is kept for a later vector select (the co-residency rule)
+__device__ inline int plane_row(const MultiPlanes &mp, int q, int ci) {
+    if (q == mp.cq) ci = mp.rowmap[ci];
+    return ci;
+}
+static void set_compact(MultiPlanes &mp, const CompactRows &cr, int B, int nbits) {
+    mp.cq = -1; mp.rowmap = nullptr; mp.cells = 0;
+    if (!cr.row_of_cell) return;
+    for (int q = 0; q < mp.n; ++q)
+        if (mp.level[q] == cr.level) { mp.cq = q; mp.rowmap = cr.row_of_cell; mp.cells = B << (2 * (nbits - cr.level)); }
+}
 template <int VEC>
 __global__ __launch_bounds__(kThreads) void segsum_bwd_multi_kernel(MultiPlanes mp, const int32_t *__restrict__ cell,
                                                                     int64_t npts, int nbits, int C, int lg,
@@ -442,7 +464,7 @@ __global__ __launch_bounds__(kThreads) void segsum_bwd_multi_kernel(MultiPlanes 
         rows[q] = nullptr;
         if (q < mp.n) {
             const int l = mp.level[q], r = 1 << (nbits - l);
-            rows[q] = mp.g[q] + (((size_t)b * r + (y0 >> l)) * r + (x0 >> l)) * mp.ld[q];
+            rows[q] = mp.g[q] + (size_t)plane_row(mp, q, (int)((b * r + (y0 >> l)) * r + (x0 >> l))) * mp.ld[q];
         }
     }
     const int span = VEC << lg;
@@ -472,7 +494,8 @@ __global__ __launch_bounds__(kThreads) void segsum_bwd_multi_kernel(MultiPlanes 
 // coarse[b, y, x, :] = fine[b, 2y, 2x, :] + fine[b, 2y, 2x+1, :] + fine[b, 2y+1, 2x, :] + fine[b, 2y+1, 2x+1, :]  (NHWC, float4 lanes):
 // the per-cell sums of resolution r / 2 from those of resolution r (a cell is the union of its four children)
 __global__ __launch_bounds__(kThreads) void plane_sumpool2x2_kernel(const float *__restrict__ fine, int64_t total4, int rc,
-                                                                   int C4, int ld_in, int ld_out, float *__restrict__ coarse) {
+                                                                   int C4, int ld_in, int ld_out, float *__restrict__ coarse,
+                                                                   const int32_t *__restrict__ rowmap) {
     int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     if (t >= total4) return;
     const int c4 = (int)(t % C4);
@@ -480,10 +503,22 @@ __global__ __launch_bounds__(kThreads) void plane_sumpool2x2_kernel(const float 
     const int x = (int)(pix % rc), y = (int)((pix / rc) % rc);
     const int64_t b = pix / ((int64_t)rc * rc);
     const int rf = 2 * rc;
-    const float *f = fine + ((b * rf + 2 * y) * rf + 2 * x) * (int64_t)ld_in + 4 * c4;
-    const float4 a = *reinterpret_cast<const float4 *>(f), bq = *reinterpret_cast<const float4 *>(f + ld_in);
-    const float4 cq = *reinterpret_cast<const float4 *>(f + (int64_t)rf * ld_in);
-    const float4 d = *reinterpret_cast<const float4 *>(f + (int64_t)rf * ld_in + ld_in);
+    const int64_t fc = (b * rf + 2 * y) * rf + 2 * x;
+    float4 a, bq, cq, d;
+    if (rowmap) {                         // compact fine rows (t2h_compact_next): an empty child has no row and contributes 0
+        const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+        const int r0 = rowmap[fc], r1 = rowmap[fc + 1], r2 = rowmap[fc + rf], r3 = rowmap[fc + rf + 1];
+        a = z; bq = z; cq = z; d = z;
+        if (r0 >= 0) a = *reinterpret_cast<const float4 *>(fine + (int64_t)r0 * ld_in + 4 * c4);
+        if (r1 >= 0) bq = *reinterpret_cast<const float4 *>(fine + (int64_t)r1 * ld_in + 4 * c4);
+        if (r2 >= 0) cq = *reinterpret_cast<const float4 *>(fine + (int64_t)r2 * ld_in + 4 * c4);
+        if (r3 >= 0) d = *reinterpret_cast<const float4 *>(fine + (int64_t)r3 * ld_in + 4 * c4);
+    } else {
+        const float *f = fine + fc * (int64_t)ld_in + 4 * c4;
+        a = *reinterpret_cast<const float4 *>(f); bq = *reinterpret_cast<const float4 *>(f + ld_in);
+        cq = *reinterpret_cast<const float4 *>(f + (int64_t)rf * ld_in);
+        d = *reinterpret_cast<const float4 *>(f + (int64_t)rf * ld_in + ld_in);
+    }
     float4 o;
     o.x = (a.x + bq.x) + (cq.x + d.x); o.y = (a.y + bq.y) + (cq.y + d.y);
     o.z = (a.z + bq.z) + (cq.z + d.z); o.w = (a.w + bq.w) + (cq.w + d.w);
@@ -654,7 +689,8 @@ __global__ __launch_bounds__(256, 2) void sample_relu_cellsums_v2_kernel(const f
                                                                         int sum_level, int C, float *__restrict__ sums,
                                                                         int ld_sums, unsigned long long *__restrict__ bits,
                                                                         int npts_m1, float *__restrict__ sums2, int ld_sums2,
-                                                                        const int32_t *__restrict__ order, int gz) {
+                                                                        const int32_t *__restrict__ order, int gz,
+                                                                        const int32_t *__restrict__ rowmap) {
     constexpr int SIDE = 3 + K, NS = SIDE * SIDE;
     __shared__ float4 T[NS][64];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -773,7 +809,11 @@ __global__ __launch_bounds__(256, 2) void sample_relu_cellsums_v2_kernel(const f
             const float4 sum = make_float4(sum01.x, sum01.y, sum23.x, sum23.y);
             const uint32_t cm = (uint32_t)(cb + c);                      // child's Morton code inside the cell
             const int fx = (cx << d) + (int)compact1by1(cm), fy = (cy << d) + (int)compact1by1(cm >> 1);
-            *reinterpret_cast<float4 *>(sums + (((size_t)b * rs + fy) * rs + fx) * ld_sums + c0) = sum;
+            // rowmap (t2h_compact_next): `sums` holds one row per occupied child; an empty child has none and writes nothing.
+            // s, e and the row are wave-uniform: a scalar branch
+            int srow = (b * rs + fy) * rs + fx;
+            if (rowmap) srow = e > s ? __builtin_amdgcn_readfirstlane(rowmap[srow]) : -1;
+            if (srow >= 0) *reinterpret_cast<float4 *>(sums + (size_t)srow * ld_sums + c0) = sum;
             if (POOL) {
                 // the 2 x 2 pooled sums one level up, formed from the four children while they are in registers (children are
                 // visited in Morton order = the order (c0 + c1) + (c2 + c3) of plane_sumpool2x2_kernel: same bits)
@@ -1115,7 +1155,8 @@ __global__ __launch_bounds__(kCellThreads) void segmean_cells_kernel(const float
 __global__ __launch_bounds__(kThreads) void segmean_finalize_kernel(const float *__restrict__ partial,
                                                                    const int32_t *__restrict__ off0, int B, int nbits,
                                                                    int level, int C, int lg, int S,
-                                                                   float *__restrict__ plane, int mean = 1, int ld_out = 0) {
+                                                                   float *__restrict__ plane, int mean = 1, int ld_out = 0,
+                                                                   const int32_t *__restrict__ rowmap = nullptr) {
     int64_t t = (int64_t)blockIdx.x * kThreads + threadIdx.x;
     int64_t gid = t >> lg;
     const int rbits = nbits - level;
@@ -1127,7 +1168,12 @@ __global__ __launch_bounds__(kThreads) void segmean_finalize_kernel(const float 
     int cnt = off0[obase + ((size_t)1 << (2 * level))] - off0[obase];
     float den = (float)(cnt > 0 ? cnt : 1);
     int cx = (int)compact1by1(mk), cy = (int)compact1by1(mk >> 1), r = 1 << rbits;
-    float *orow = plane + (((size_t)b * r + cy) * r + cx) * (ld_out > 0 ? ld_out : C);
+    int64_t orow_i = ((int64_t)b * r + cy) * r + cx;
+    if (rowmap) {                         // compact rows (t2h_compact_next): an empty cell has no row and writes nothing
+        if (cnt <= 0) return;
+        orow_i = rowmap[orow_i];
+    }
+    float *orow = plane + (size_t)orow_i * (ld_out > 0 ? ld_out : C);
     for (int c = ((int)t & ((1 << lg) - 1)) * 4; c < C; c += 4 << lg) {
         float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
         for (int sp = 0; sp < S; ++sp) {
@@ -1186,7 +1232,8 @@ __global__ __launch_bounds__(kCellThreads) void sample_bwd_cells_kernel(const fl
                 for (int q = 0; q < kMaxMultiPlanes; ++q)
                     if (q < mp.n) {
                         const int l = mp.level[q], rq = 1 << (nbits - l);
-                        const float4 u = *reinterpret_cast<const float4 *>(mp.g[q] + (((size_t)fb * rq + (fy >> l)) * rq + (fx >> l)) * mp.ld[q] + c);
+                        const float4 u = *reinterpret_cast<const float4 *>(
+                            mp.g[q] + (size_t)plane_row(mp, q, (int)((fb * rq + (fy >> l)) * rq + (fx >> l))) * mp.ld[q] + c);
                         if (q == 0) g = u;
                         else { g.x = __fadd_rn(g.x, u.x); g.y = __fadd_rn(g.y, u.y); g.z = __fadd_rn(g.z, u.z); g.w = __fadd_rn(g.w, u.w); }
                     }
@@ -1301,8 +1348,10 @@ __global__ __launch_bounds__(kCellThreads) void sample_bwd_cells_mfma_kernel(con
                 for (int q = 0; q < kMaxMultiPlanes; ++q)
                     if (q < mp.n && mp.level[q] >= tlevel) {
                         const int l = mp.level[q], rq = 1 << (nbits - l), sh = l - tlevel;
-                        const float4 w = *reinterpret_cast<const float4 *>(
-                            mp.g[q] + (((size_t)b * rq + (ty >> sh)) * rq + (tx >> sh)) * mp.ld[q] + che);
+                        // (a compacted plane: an empty child has no row -- and no row of this cell points at its table entry)
+                        const int prow = plane_row(mp, q, (int)((b * rq + (ty >> sh)) * rq + (tx >> sh)));
+                        if (prow < 0) continue;
+                        const float4 w = *reinterpret_cast<const float4 *>(mp.g[q] + (size_t)prow * mp.ld[q] + che);
                         v.x = __fadd_rn(v.x, w.x); v.y = __fadd_rn(v.y, w.y); v.z = __fadd_rn(v.z, w.z); v.w = __fadd_rn(v.w, w.w);
                     }
                 Tl[t][c4] = v;
@@ -1346,7 +1395,7 @@ __global__ __launch_bounds__(kCellThreads) void sample_bwd_cells_mfma_kernel(con
                 for (int q = 0; q < kMaxMultiPlanes; ++q)
                     if (q < mp.n) {
                         const int l = mp.level[q], rq = 1 << (nbits - l);
-                        Po[tid][q] = (int)((fb * rq + (fy >> l)) * rq + (fx >> l));
+                        Po[tid][q] = plane_row(mp, q, (int)((fb * rq + (fy >> l)) * rq + (fx >> l)));
                     }
                 if (tlevel >= 0) Ti[tid] = (int)((fm >> (2 * tlevel)) & ((1u << (2 * (level - tlevel))) - 1u));
             }
@@ -1487,6 +1536,9 @@ __global__ __launch_bounds__(256) void sample_bwd_walk_kernel(const float *__res
             if (q < mp.n) {
                 const int sh = mp.level[q] - wl, rq = 1 << (nbits - mp.level[q]);
                 prow_l[q] = (b * rq + (fy >> sh)) * rq + (fx >> sh);
+                // compacted plane: the child's row (-1 for an empty child, which is never requested); lanes past the last child
+                // hold no cell -- their index is clamped into the map by arithmetic
+                if (q == mp.cq) prow_l[q] = mp.rowmap[min(max(prow_l[q], 0), mp.cells - 1)];
             }
     };
     auto request = [&](int c) {                                         // c: the child's lane in the current batch (uniform)
@@ -1891,8 +1943,11 @@ T2H_API int t2h_pool_rows_bwd(const float *gpooled, int ldg, const uint8_t *winn
 }
 
 static int segreduce_fwd(bool mean, const float *feat, const int32_t *off0, int B, int N, int nbits, int level, int C,
-                         float *plane_nhwc, int ld_out, void *workspace, size_t workspace_bytes, t2h_stream_t stream) {
+                         float *plane_nhwc, int ld_out, void *workspace, size_t workspace_bytes, t2h_stream_t stream,
+                         const CompactRows &cr = CompactRows{}) {
     if (!feat || !off0 || !plane_nhwc) return fail(T2H_ERR_ARG, "segmean_fwd: null pointer");
+    if (cr.row_of_cell && cr.level != level) return fail(T2H_ERR_ARG, "segsum_fwd: compact rows of level %d asked for level %d", cr.level, level);
+    const int32_t *rowmap = cr.row_of_cell;
     if (ld_out < C || (C % 4 == 0 && ld_out % 4 != 0)) return fail(T2H_ERR_ARG, "segmean_fwd: plane row stride %d < C = %d", ld_out, C);
     int rc = check_level("segmean_fwd", B, nbits, level, C);
     if (rc) return rc;
@@ -1909,25 +1964,25 @@ static int segreduce_fwd(bool mean, const float *feat, const int32_t *off0, int 
                            partial);
         GroupCfg g = group_cfg<4>(C);
         hipLaunchKernelGGL(segmean_finalize_kernel, dim3(grid_for(groups, g.lg)), dim3(kThreads), 0, as_stream(stream),
-                           partial, off0, B, nbits, level, C, g.lg, cp.S, plane_nhwc, mean ? 1 : 0, ld_out);
+                           partial, off0, B, nbits, level, C, g.lg, cp.S, plane_nhwc, mean ? 1 : 0, ld_out, rowmap);
         return check_launch("segmean_fwd(coarse)");
     }
     if (mean) {
         T2H_DISPATCH_VEC(C,
             { GroupCfg g = group_cfg<4>(C);
               hipLaunchKernelGGL(segmean_fwd_kernel<4>, dim3(grid_for(groups, g.lg)), dim3(kThreads), 0, as_stream(stream),
-                                 feat, off0, B, nbits, level, C, g.lg, plane_nhwc, ld_out); },
+                                 feat, off0, B, nbits, level, C, g.lg, plane_nhwc, ld_out, rowmap); },
             { GroupCfg g = group_cfg<1>(C);
               hipLaunchKernelGGL(segmean_fwd_kernel<1>, dim3(grid_for(groups, g.lg)), dim3(kThreads), 0, as_stream(stream),
-                                 feat, off0, B, nbits, level, C, g.lg, plane_nhwc, ld_out); });
+                                 feat, off0, B, nbits, level, C, g.lg, plane_nhwc, ld_out, rowmap); });
     } else {
         T2H_DISPATCH_VEC(C,
             { GroupCfg g = group_cfg<4>(C);
               hipLaunchKernelGGL((segmean_fwd_kernel<4, false>), dim3(grid_for(groups, g.lg)), dim3(kThreads), 0, as_stream(stream),
-                                 feat, off0, B, nbits, level, C, g.lg, plane_nhwc, ld_out); },
+                                 feat, off0, B, nbits, level, C, g.lg, plane_nhwc, ld_out, rowmap); },
             { GroupCfg g = group_cfg<1>(C);
               hipLaunchKernelGGL((segmean_fwd_kernel<1, false>), dim3(grid_for(groups, g.lg)), dim3(kThreads), 0, as_stream(stream),
-                                 feat, off0, B, nbits, level, C, g.lg, plane_nhwc, ld_out); });
+                                 feat, off0, B, nbits, level, C, g.lg, plane_nhwc, ld_out, rowmap); });
     }
     return check_launch("segmean_fwd");
 }
@@ -1939,11 +1994,13 @@ T2H_API int t2h_segmean_fwd(const float *feat, const int32_t *off0, int B, int N
 
 T2H_API int t2h_segsum_fwd(const float *feat, const int32_t *off0, int B, int N, int nbits, int level, int C,
                            float *plane_nhwc, int ld_plane, void *workspace, size_t workspace_bytes, t2h_stream_t stream) {
-    return segreduce_fwd(false, feat, off0, B, N, nbits, level, C, plane_nhwc, ld_plane, workspace, workspace_bytes, stream);
+    const CompactRows cr = take_compact();
+    return segreduce_fwd(false, feat, off0, B, N, nbits, level, C, plane_nhwc, ld_plane, workspace, workspace_bytes, stream, cr);
 }
 
 T2H_API int t2h_plane_sumpool2x2(const float *fine_nhwc, int ld_fine, int B, int r_fine, int C, float *coarse_nhwc, int ld_coarse,
                                  t2h_stream_t stream) {
+    const CompactRows cr = take_compact();      // (the FINE side's rows; the level is the caller's to match: r_fine says nothing of it)
     if (!fine_nhwc || !coarse_nhwc) return fail(T2H_ERR_ARG, "plane_sumpool2x2: null pointer");
     if (B < 1 || r_fine < 2 || (r_fine & 1) || C < 4 || C % 4 != 0 || ((uintptr_t)fine_nhwc & 15) || ((uintptr_t)coarse_nhwc & 15) ||
         ld_fine < C || ld_coarse < C || ld_fine % 4 != 0 || ld_coarse % 4 != 0)
@@ -1951,13 +2008,15 @@ T2H_API int t2h_plane_sumpool2x2(const float *fine_nhwc, int ld_fine, int B, int
     const int rc = r_fine / 2;
     const int64_t total4 = (int64_t)B * rc * rc * (C / 4);
     hipLaunchKernelGGL(plane_sumpool2x2_kernel, dim3((unsigned)((total4 + kThreads - 1) / kThreads)), dim3(kThreads), 0,
-                       as_stream(stream), fine_nhwc, total4, rc, C / 4, ld_fine, ld_coarse, coarse_nhwc);
+                       as_stream(stream), fine_nhwc, total4, rc, C / 4, ld_fine, ld_coarse, coarse_nhwc,
+                       cr.row_of_cell);
     return check_launch("plane_sumpool2x2");
 }
 
 T2H_API int t2h_segsum_bwd_multi(const float *const *gplanes_nhwc, const int *levels, const int *lds, int n_planes,
                                  const int32_t *cell, int B, int N, int nbits, int C, const float *mask, const float *addend,
                                  float *gfeat, t2h_stream_t stream) {
+    const CompactRows cr = take_compact();
     if (!gplanes_nhwc || !levels || !lds || !cell || !gfeat) return fail(T2H_ERR_ARG, "segsum_bwd_multi: null pointer");
     if (n_planes < 1 || n_planes > kMaxMultiPlanes)
         return fail(T2H_ERR_ARG, "segsum_bwd_multi: 1..%d planes, got %d", kMaxMultiPlanes, n_planes);
@@ -1972,6 +2031,7 @@ T2H_API int t2h_segsum_bwd_multi(const float *const *gplanes_nhwc, const int *le
     }
     if (C % 4 == 0 && ((mask && ((uintptr_t)mask & 15)) || (addend && ((uintptr_t)addend & 15)) || ((uintptr_t)gfeat & 15)))
         return fail(T2H_ERR_ARG, "segsum_bwd_multi: rows must be 16-byte aligned");
+    set_compact(mp, cr, B, nbits);
     const int64_t npts = rows_of(B, N);
     if (npts == 0) return T2H_OK;
     T2H_DISPATCH_VEC(C,
@@ -2062,7 +2122,11 @@ T2H_API int t2h_sample_relu_cellsums_ordered(const float *plane_nhwc, const floa
                                              int nbits, int level, int sum_level, int C, float *sums_nhwc, int ld_sums,
                                              float *pooled_nhwc, int ld_pooled, void *sign_bits, const int32_t *cell_order,
                                              t2h_stream_t stream) {
+    const CompactRows cr = take_compact();
     if (!plane_nhwc || !pts || !off0 || !sums_nhwc) return fail(T2H_ERR_ARG, "sample_relu_cellsums: null pointer");
+    if (cr.row_of_cell && cr.level != sum_level)
+        return fail(T2H_ERR_ARG, "sample_relu_cellsums: compact rows of level %d asked for the sums of level %d", cr.level, sum_level);
+    const int32_t *rowmap = cr.row_of_cell;
     if (pooled_nhwc && (sum_level >= level || ld_pooled < C || ld_pooled % 4 != 0 || ((uintptr_t)pooled_nhwc & 15)))
         return fail(T2H_ERR_ARG, "sample_relu_cellsums: the pooled sums need sum_level < level and 16-byte aligned rows of >= C floats");
     int rc = check_level("sample_relu_cellsums", B, nbits, level, C);
@@ -2089,7 +2153,7 @@ T2H_API int t2h_sample_relu_cellsums_ordered(const float *plane_nhwc, const floa
     if (k0) while (nchild / (4 * gz * 2) >= quad && cells * chunks * gz < kMinWgs) gz *= 2;
     const dim3 grid((unsigned)((k0 ? cells : (cells >> 2)) * chunks * gz));               // K = 1: a 2 x 2 block of cells per workgroup
 #define T2H_V2_LAUNCH(KK, PP) hipLaunchKernelGGL((sample_relu_cellsums_v2_kernel<KK, PP>), grid, dim3(256), 0, as_stream(stream), \
-        plane_nhwc, pts, dim, off0, nbits, level, sum_level, C, sums_nhwc, ld_sums, bw, npts_m1, pooled_nhwc, ld_pooled, k0 ? order_k0 : order_k1, gz)
+        plane_nhwc, pts, dim, off0, nbits, level, sum_level, C, sums_nhwc, ld_sums, bw, npts_m1, pooled_nhwc, ld_pooled, k0 ? order_k0 : order_k1, gz, rowmap)
     if (k0) { if (pooled_nhwc) T2H_V2_LAUNCH(0, true); else T2H_V2_LAUNCH(0, false); }
     else { if (pooled_nhwc) T2H_V2_LAUNCH(1, true); else T2H_V2_LAUNCH(1, false); }
 #undef T2H_V2_LAUNCH
@@ -2109,6 +2173,7 @@ T2H_API int t2h_sample_bwd_from_sums_ordered(const float *const *gplanes_nhwc, c
                                              const int32_t *off0, int B, int N, int nbits, int level, int C, float *gplane_nhwc,
                                              void *workspace, size_t workspace_bytes, const int32_t *cell_order,
                                              t2h_stream_t stream) {
+    const CompactRows cr = take_compact();
     if (!gplanes_nhwc || !levels || !lds || !cell || !mask || !pts || !off0 || !gplane_nhwc)
         return fail(T2H_ERR_ARG, "sample_bwd_from_sums: null pointer");
     if (n_planes < 1 || n_planes > kMaxMultiPlanes)
@@ -2133,6 +2198,7 @@ T2H_API int t2h_sample_bwd_from_sums_ordered(const float *const *gplanes_nhwc, c
             return fail(T2H_ERR_ARG, "sample_bwd_from_sums: bad plane %d", q);
         mp.g[q] = gplanes_nhwc[q]; mp.level[q] = levels[q]; mp.ld[q] = lds[q];
     }
+    set_compact(mp, cr, B, nbits);
     int64_t groups = (int64_t)B << (2 * (nbits - level));
     float *partial = static_cast<float *>(workspace);
     int G = 1 << cp.lgG, P = kCellThreads >> cp.lgG;

@@ -34,6 +34,11 @@ FUSED_SAMPLE_BWD = os.environ.get("T2H_FUSED_SAMPLE_BWD", "1") != "0"      # A/B
 CELLS_MFMA = os.environ.get("T2H_CELLS_MFMA", "1") != "0"                  # (mirrors the library's switch: the bit mask needs it)
 SIGN_BITS = os.environ.get("T2H_SIGN_BITS", "1") != "0"                    # A/B: 0 = keep the hidden activations for the mask
 ON_CHIP_HIDDEN = os.environ.get("T2H_ON_CHIP_HIDDEN", "1") != "0"          # A/B: 0 = sample kernel + per-cell sum kernel
+# A/B: 0 = one row per CELL in the sum matrices of every resolution.  1: the matrices of the finest deferred resolution hold one row
+# per OCCUPIED cell (cell_rows; decided statically per level -- the occupied fraction is known on the device only, and a host read
+# of it would be a sync in the step; where every cell is occupied, compact and dense rows coincide)
+COMPACT_SUMS = os.environ.get("T2H_COMPACT_SUMS", "1") != "0"
+_empty = torch.empty          # allocator of the sum / gradient / product matrices (tests fill the new memory with NaN through it)
 ON_CHIP_MIN_PTS_PER_CELL = float(os.environ.get("T2H_ON_CHIP_MIN_PTS", "8"))   # the walk is sequential inside a cell
 
 
@@ -42,22 +47,27 @@ ON_CHIP_MIN_PTS_PER_CELL = float(os.environ.get("T2H_ON_CHIP_MIN_PTS", "8"))   #
 # order they appear (base features, h of the first deferred level, h of the second, ...).  A level's scatter_mean is then a single
 # product over the leading K_k columns (all sources that exist at that level), its backward a single product into the gradient
 # matrix dS_lv of the same layout, and a source's kernels address "their" block through a row stride.
-def _segsum_into(tile, rows, level, dst):
-    """Per-cell sums of ``rows`` [N, C] at ALTO level ``level`` into the [B r r, C] column block ``dst`` (row stride dst.stride(0))."""
+def _segsum_into(tile, rows, level, dst, state=None):
+    """Per-cell sums of ``rows`` [N, C] at ALTO level ``level`` into the [B r r, C] column block ``dst`` (row stride dst.stride(0));
+    ``state``: the ``Deferred`` whose matrix ``dst`` belongs to (its compact level is addressed by occupied row)."""
     n, c = rows.shape
     r = tile.R >> level
     ws_bytes = _lib.ws_bytes("t2h_segmean_workspace_bytes", tile.B, tile.N, tile.nbits, level, c)
     ws = _lib.workspace(ws_bytes, rows.device)
+    if state is not None:
+        state.request(level)
     _lib.call("t2h_segsum_fwd", _lib.ptr(rows), _lib.ptr(tile.off0), tile.B, tile.N, tile.nbits, level, c, dst.data_ptr(),
               dst.stride(0), _lib.ptr(ws), ws_bytes, _lib.stream(), nbytes=4 * c * n + 4 * n + 4 * c * tile.B * r * r,
               tag=_lib.timing() and f"t2h_segsum_fwd[C={c},r={r}]")
 
 
-def _sumpool_into(tile, fine, level_fine, coarse):
+def _sumpool_into(tile, fine, level_fine, coarse, state=None):
     """Sums at ``level_fine`` (column block ``fine``) -> level_fine + 1 (column block ``coarse``): a cell is the union of its four
     children."""
     c = fine.shape[1]
     r = tile.R >> level_fine
+    if state is not None:
+        state.request(level_fine)
     _lib.call("t2h_plane_sumpool2x2", fine.data_ptr(), fine.stride(0), tile.B, r, c, coarse.data_ptr(), coarse.stride(0),
               _lib.stream(), nbytes=5 * c * tile.B * r * r, tag=_lib.timing() and f"t2h_plane_sumpool2x2[C={c}]")
 
@@ -70,15 +80,38 @@ def _plane_args(planes):
     return ctypes.cast(arr, ctypes.c_void_p), ctypes.cast(lvs, ctypes.c_void_p), ctypes.cast(lds, ctypes.c_void_p)
 
 
-def _gather(tile, planes, c, mask=None):
+def _gather(tile, planes, c, mask=None, state=None):
     """d rows [N, C] = (mask > 0 ?) sum over ``planes`` [(column block, level)] of block[cell_level(n)]: the adjoint of the sums."""
     out = torch.empty(tile.n_points, c, dtype=torch.float32, device=tile.device)
     arr, lvs, lds = _plane_args(planes)
+    if state is not None:
+        state.request_any(lv for _, lv in planes)
     _lib.call("t2h_segsum_bwd_multi", arr, lvs, lds, len(planes), _lib.ptr(tile.cell), tile.B, tile.N, tile.nbits, c,
               None if mask is None else _lib.ptr(mask), None, _lib.ptr(out), _lib.stream(),
               nbytes=4 * c * tile.n_points * (2 if mask is not None else 1) + 4 * tile.n_points
               + sum(4 * c * p.shape[0] for p, _ in planes), tag=_lib.timing() and f"t2h_segsum_bwd_multi[C={c},n={len(planes)}]")
     return out
+
+
+def cell_rows(tile, level):
+    """The occupied-row list of ALTO level ``level`` (include/t2h.h, ``t2h_compact_next``): one int32 buffer ``row_of_cell [P] |
+    cell_of_row [P] | n_rows | ...`` with P = B r r, built on first use by the same entry point as the counts and kept for the
+    tile's lifetime with the event behind its fill.  ``n_rows`` stays on the device: nothing here reads it."""
+    cache = tile.__dict__.setdefault("_cell_rows", {})
+    hit = cache.get(level)
+    if hit is None:
+        r = tile.R >> level
+        p = tile.B * r * r
+        buf = torch.empty(2 * p + 4 + (p + 2047) // 2048, dtype=torch.int32, device=tile.device)
+        cnt = torch.empty(p, dtype=torch.float32, device=tile.device)
+        _lib.compact_next(buf.data_ptr(), level, buf.data_ptr() + 8 * p)
+        _lib.call("t2h_cell_counts", _lib.ptr(tile.off0), tile.B, tile.nbits, level, _lib.ptr(cnt), _lib.stream(), nbytes=28 * p)
+        tile.__dict__.setdefault("_cell_counts", {}).setdefault(level, cnt)      # the counts came out of the same launch: counts() finds them
+        ready = _lib.Ready()
+        ready.mark()
+        hit = cache[level] = (buf, ready)
+    hit[1].wait()
+    return hit[0]
 
 
 def counts(tile, level):
@@ -185,6 +218,7 @@ class _DeferredLevel(torch.autograd.Function):
             if len(levels) > 1 and levels[1] == levels[0] + 1 and levels[0] < tile.level(r):
                 second = state.sums(idx + 1, levels[1])
             order = tile.cell_order(tile.level(r))
+            state.request(levels[0])
             _lib.call("t2h_sample_relu_cellsums_ordered", _lib.ptr(q_rows), _lib.ptr(tile.pts), tile.dim, _lib.ptr(tile.off0), tile.B,
                       tile.N, tile.nbits, tile.level(r), levels[0], c2, finest.data_ptr(), finest.stride(0),
                       None if second is None else second.data_ptr(), 0 if second is None else second.stride(0),
@@ -208,10 +242,11 @@ class _DeferredLevel(torch.autograd.Function):
         if a_all.shape[0] != k:
             raise RuntimeError(f"deferred level {idx}: {a_all.shape[0]} composed rows for {k} source columns")
         x = state.S[lv][:, :k]
-        acc = torch.empty(x.shape[0], a_all.shape[1], dtype=torch.float32, device=x.device)
-        mlp.linear_dgrad_(x, a_all, acc, bx3=True)                         # "dx = dy w" is exactly x @ A
+        acc = _empty(x.shape[0], a_all.shape[1], dtype=torch.float32, device=x.device)
+        mlp.linear_dgrad_(x, a_all, acc, bx3=True, row_limit=state.row_limit(lv))     # "dx = dy w" is exactly x @ A
         cnt = counts(tile, lv)
         out = torch.empty_like(acc)
+        state.request(lv)
         _lib.call("t2h_mean_bias_fwd", _lib.ptr(acc), _lib.ptr(cnt), _lib.ptr(const), acc.shape[0], acc.shape[1], _lib.ptr(out),
                   _lib.stream(), nbytes=8 * acc.numel() + 4 * acc.shape[0])
         ctx.state, ctx.idx, ctx.r, ctx.has_base = state, idx, r, idx == 0
@@ -233,11 +268,13 @@ class _DeferredLevel(torch.autograd.Function):
         p, c = g.shape
         cnt = counts(tile, lv)
         # through the mean / bias epilogue
-        dacc = torch.empty_like(g)
+        dacc = _empty(g.shape, dtype=torch.float32, device=g.device)
+        lim = state.row_limit(lv)
         cached = state.cache is not None and not ctx.needs_input_grad[1]      # maps from the trainer's ComposeCache
         dconst = torch.empty(ctx.const_shape, dtype=torch.float32, device=g.device) if (ctx.needs_input_grad[2] or cached) else None
         ws_bytes = _lib.ws_bytes("t2h_mean_bias_bwd_workspace_bytes", p, c)
         ws = _lib.workspace(ws_bytes, g.device)
+        state.request(lv)
         _lib.call("t2h_mean_bias_bwd", _lib.ptr(g), _lib.ptr(cnt), p, c, _lib.ptr(dacc), None if dconst is None else _lib.ptr(dconst),
                   _lib.ptr(ws), ws_bytes, _lib.stream(), nbytes=8 * p * c + 4 * p)
         x = state.S[lv][:, :k]
@@ -246,16 +283,16 @@ class _DeferredLevel(torch.autograd.Function):
             # this tile's share goes onto the persistent sums (zeroed by flush())
             e = state.cache.levels[idx]
             e.ready.wait()
-            mlp.linear_wgrad_(x, dacc, e.ga, None, accumulate=True, defer=True)      # += x^T dacc (read at flush(): after the pass)
+            mlp.linear_wgrad_(x, dacc, e.ga, None, accumulate=True, defer=True, row_limit=lim)   # += x^T dacc (read at flush())
             e.gconst.add_(dconst)
             dconst = None
             state.cache.pending = True
         elif ctx.needs_input_grad[1]:
             if ga_thru is not None and ga_thru.is_contiguous() and ga_thru.dtype == torch.float32 and mlp.sole_owner(ga_thru):
-                mlp.linear_wgrad_(x, dacc, ga_thru, None, accumulate=True)  # x^T dacc, onto the next level's share
+                mlp.linear_wgrad_(x, dacc, ga_thru, None, accumulate=True, row_limit=lim)   # x^T dacc, onto the next level's share
             else:
                 da = torch.empty_like(a_all)
-                mlp.linear_wgrad_(x, dacc, da, None)                       # x^T dacc
+                mlp.linear_wgrad_(x, dacc, da, None, row_limit=lim)        # x^T dacc
                 if ga_thru is not None:
                     da = da + ga_thru
         # into the gradient matrix of this resolution: the leading k columns; a later level of the same resolution (run before,
@@ -263,7 +300,7 @@ class _DeferredLevel(torch.autograd.Function):
         dS, seen = state.grad_matrix(lv)
         if seen and seen < k:
             raise RuntimeError("deferred backward out of order")
-        mlp.linear_fwd_(dacc, a_all, None, dS[:, :k], accumulate=bool(seen), bx3=True)   # dacc @ A^T
+        mlp.linear_fwd_(dacc, a_all, None, dS[:, :k], accumulate=bool(seen), bx3=True, row_limit=lim)   # dacc @ A^T
         state.dS_cols[lv] = max(seen, k)
         # this level's own source: every level that used its sums has contributed by now
         lo, hi = state.off[idx + 1], state.off[idx + 2]
@@ -274,7 +311,7 @@ class _DeferredLevel(torch.autograd.Function):
         dbase = None
         if ctx.has_base and ctx.needs_input_grad[3]:
             lo0, hi0 = state.off[0], state.off[1]
-            dbase = _gather(tile, [(state.dS[l][:, lo0:hi0], l) for l in state.needed(0)], hi0 - lo0)
+            dbase = _gather(tile, [(state.dS[l][:, lo0:hi0], l) for l in state.needed(0)], hi0 - lo0, state=state)
         return dq, da, dconst, dbase, None, None, None
 
 
@@ -390,8 +427,29 @@ class Deferred:
             self.off.append(self.off[-1] + kk)
         self.base = base_rows
         self.S, self.dS, self.dS_cols = {}, {}, {}
+        # the finest deferred resolution's matrices by occupied row (COMPACT_SUMS; the row-limited weight gradient is the fp32 kernel's)
+        self.compact_lv, self.rows = None, None
+        if COMPACT_SUMS and mlp._MODE == "fp32" and tile.n_points > 0:
+            self.compact_lv = min(self.levels_seq)
+            self.rows = cell_rows(tile, self.compact_lv)
+            r = tile.R >> self.compact_lv
+            self._row_ptr, self._n_rows_ptr = self.rows.data_ptr(), self.rows.data_ptr() + 8 * tile.B * r * r
         self.a_all, self.const = None, None
         self.n_done = 0
+
+    def request(self, lv):
+        """Before a launch that touches the sum / gradient matrix of ALTO level ``lv``: ask for addressing by occupied row where
+        that level is the compact one (``t2h_compact_next``; the launch takes the request)."""
+        if lv == self.compact_lv:
+            _lib.compact_next(self._row_ptr, lv, self._n_rows_ptr)
+
+    def request_any(self, levels):
+        if self.compact_lv is not None and self.compact_lv in levels:
+            self.request(self.compact_lv)
+
+    def row_limit(self, lv):
+        """Device pointer to the number of rows in use of level ``lv``'s matrices, None where they hold one row per cell."""
+        return self._n_rows_ptr if lv == self.compact_lv else None
 
     def needed(self, src):
         """ALTO levels (finest first) at which source ``src`` is rasterised: the resolutions of its own level and all later ones."""
@@ -401,7 +459,7 @@ class Deferred:
     def _matrix(self, store, lv):
         if lv not in store:
             r = self.tile.R >> lv
-            store[lv] = torch.empty(self.tile.B * r * r, self.off[-1], dtype=torch.float32, device=self.tile.device)
+            store[lv] = _empty(self.tile.B * r * r, self.off[-1], dtype=torch.float32, device=self.tile.device)
         return store[lv]
 
     def sums(self, src, lv):
@@ -415,7 +473,7 @@ class Deferred:
         """Per-cell sums of ``rows`` [N, K_src] into the source's column block at every needed resolution: the finest from the
         rows (read once), the coarser ones by 2x2 pooling."""
         finest = self.needed(src)[0]
-        _segsum_into(self.tile, rows, finest, self.sums(src, finest))
+        _segsum_into(self.tile, rows, finest, self.sums(src, finest), self)
         self.pool_down(src)
 
     def pool_down(self, src, start=0):
@@ -432,7 +490,7 @@ class Deferred:
                 else:                                       # a resolution no level uses: a compact temporary on the way down
                     rn = self.tile.R >> nxt_level
                     nxt = torch.empty(self.tile.B * rn * rn, cur.shape[1], dtype=torch.float32, device=cur.device)
-                _sumpool_into(self.tile, cur, cur_level, nxt)
+                _sumpool_into(self.tile, cur, cur_level, nxt, self)
                 cur, cur_level = nxt, nxt_level
 
     def hidden_grad(self, planes, h, r, c2, mask_is_bits=False):
@@ -446,13 +504,14 @@ class Deferred:
             ws = _lib.workspace(ws_bytes, h.device)
             dq = torch.empty(tile.B * r * r, c2, dtype=torch.float32, device=h.device)
             order = tile.cell_order(level) if mask_is_bits else None
+            self.request_any([lv for _, lv in planes])
             _lib.call("t2h_sample_bwd_from_sums_ordered", arr, lvs, lds, len(planes), _lib.ptr(tile.cell), _lib.ptr(h),
                       1 if mask_is_bits else 0, _lib.ptr(tile.pts), tile.dim, _lib.ptr(tile.off0), tile.B, tile.N, tile.nbits,
                       level, c2, _lib.ptr(dq), _lib.ptr(ws), ws_bytes, None if order is None else _lib.ptr(order), _lib.stream(),
                       nbytes=(c2 // 8 if mask_is_bits else 4 * c2) * tile.n_points + 12 * tile.n_points + 4 * dq.numel()
                       + sum(4 * c2 * p.shape[0] for p, _ in planes), tag=_lib.timing() and f"t2h_sample_bwd_from_sums[C={c2},r={r}]")
             return dq
-        dh = _gather(tile, planes, c2, mask=h)
+        dh = _gather(tile, planes, c2, mask=h, state=self)
         return ops._sample_bwd(tile, dh, r, c2, None).reshape(tile.B * r * r, c2)
 
     def advance(self, q_rows, r, fc_b, fc_c):

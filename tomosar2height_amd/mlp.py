@@ -84,7 +84,7 @@ def _bx3_gemm_ok(m, k, n, *rows, force=False) -> bool:
     return force or wide_short or (n >= min_n and k >= min_k and m >= 4096)
 
 
-def _gemm_bx3(x, w, w_is_kn, bias, mask, y, relu_out, accumulate, tag):
+def _gemm_bx3(x, w, w_is_kn, bias, mask, y, relu_out, accumulate, tag, row_limit=None):
     from . import grid
     (xp, ldx), (yp, ldy) = _rows(x, "gemm_bx3 x"), _rows(y, "gemm_bx3 y")
     m, k = x.shape
@@ -93,20 +93,25 @@ def _gemm_bx3(x, w, w_is_kn, bias, mask, y, relu_out, accumulate, tag):
     nws = _lib.ws_bytes("t2h_gemm_bx3_workspace_bytes", m, k, n)
     ws = _lib.workspace(nws, x.device)
     flags = (_lib.RELU_OUT if relu_out else 0) | (_lib.ACCUM if accumulate else 0) | (_lib.F16X2 if grid._h2() else 0)
-    _lib.call("t2h_gemm_bx3", xp, ldx, _lib.ptr(grid.split_weights.get_gemm(w, w_is_kn)), bias.data_ptr() if bias is not None else None,
+    wf = _lib.ptr(grid.split_weights.get_gemm(w, w_is_kn))               # (may launch the split: before the request below)
+    if row_limit is not None:
+        _lib.compact_next(None, -1, row_limit)
+    _lib.call("t2h_gemm_bx3", xp, ldx, wf, bias.data_ptr() if bias is not None else None,
               mp, ldm, yp, ldy, m, k, n, flags, _lib.ptr(ws), nws, _lib.stream(),
               nbytes=4 * (m * k + m * n + n * k + (m * n if mask is not None else 0)), flops=2 * m * k * n, tag=_lib.timing() and tag)
     return y
 
 
-def linear_fwd_(x, w, bias, y, relu_in=False, relu_out=False, accumulate=False, bx3=False):
+def linear_fwd_(x, w, bias, y, relu_in=False, relu_out=False, accumulate=False, bx3=False, row_limit=None):
     """y = [y +] act_out(act_in(x) w^T + bias), written in place into ``y`` (may be a column slice).  ``bx3``: the caller's
-    product is a grid-side one with a weight that lives across calls (split once): take the split-bf16 matrix-core kernel."""
+    product is a grid-side one with a weight that lives across calls (split once): take the split-bf16 matrix-core kernel.
+    ``row_limit``: device pointer to an int -- only the first ``*row_limit`` rows of x / y are in use (compact per-cell matrices,
+    deferred.py); the split kernel stops there, the fp32 kernels compute the unused rows too (nobody reads them)."""
     (xp, ldx), (yp, ldy) = _rows(x, "linear_fwd x"), _rows(y, "linear_fwd y")
     m, k = x.shape
     n = w.shape[0]
     if bx3 and not relu_in and w.is_contiguous() and _bx3_gemm_ok(m, k, n, x, y):
-        return _gemm_bx3(x, w, False, bias, None, y, relu_out, accumulate, f"t2h_linear_fwd[K={k},N={n}]")
+        return _gemm_bx3(x, w, False, bias, None, y, relu_out, accumulate, f"t2h_linear_fwd[K={k},N={n}]", row_limit)
     w = w.contiguous()
     flags = (_lib.RELU_IN if relu_in else 0) | (_lib.RELU_OUT if relu_out else 0) | (_lib.ACCUM if accumulate else 0) | _pflag()
     _lib.call("t2h_linear_fwd", xp, ldx, w.data_ptr(), bias.data_ptr() if bias is not None else None, yp, ldy, m, k, n,
@@ -115,13 +120,13 @@ def linear_fwd_(x, w, bias, y, relu_in=False, relu_out=False, accumulate=False, 
     return y
 
 
-def linear_dgrad_(dy, w, dx, mask=None, accumulate=False, bx3=False):
-    """dx = [dx +] (dy w) * (mask > 0), in place into ``dx``.  ``bx3``: see ``linear_fwd_``."""
+def linear_dgrad_(dy, w, dx, mask=None, accumulate=False, bx3=False, row_limit=None):
+    """dx = [dx +] (dy w) * (mask > 0), in place into ``dx``.  ``bx3``, ``row_limit``: see ``linear_fwd_``."""
     (gp, ldg), (dp, ldd) = _rows(dy, "linear_dgrad dy"), _rows(dx, "linear_dgrad dx")
     m, n = dy.shape
     k = w.shape[1]
     if bx3 and w.is_contiguous() and _bx3_gemm_ok(m, n, k, dy, dx, mask):
-        return _gemm_bx3(dy, w, True, None, mask, dx, False, accumulate, f"t2h_linear_dgrad[N={n},K={k}]")
+        return _gemm_bx3(dy, w, True, None, mask, dx, False, accumulate, f"t2h_linear_dgrad[N={n},K={k}]", row_limit)
     w = w.contiguous()
     mp, ldm = (None, 0) if mask is None else _rows(mask, "linear_dgrad mask")
     _lib.call("t2h_linear_dgrad", gp, ldg, w.data_ptr(), dp, ldd, m, k, n, mp, ldm,
@@ -136,9 +141,11 @@ def _grid_h2() -> bool:
     return grid._h2()
 
 
-def linear_wgrad_(dy, x, dw, db, relu_in=False, accumulate=False, defer=False):
+def linear_wgrad_(dy, x, dw, db, relu_in=False, accumulate=False, defer=False, row_limit=None):
     """dw = [dw +] dy^T act_in(x); db = [db +] colsum(dy) (db may be None); deterministic split reduction.  ``defer``: dw / db are
-    buffers nobody reads before the backward pass ends: the reduction may join the pass's batched one (``_lib.reduce_capture``)."""
+    buffers nobody reads before the backward pass ends: the reduction may join the pass's batched one (``_lib.reduce_capture``).
+    ``row_limit``: device pointer to an int -- the sum runs over the first ``*row_limit`` rows only, the rows behind them may hold
+    anything (compact per-cell matrices, deferred.py): the fp32 kernel, whose loader masks them."""
     (gp, ldg), (xp, ldx) = _rows(dy, "linear_wgrad dy"), _rows(x, "linear_wgrad x")
     m, n = dy.shape
     k = x.shape[1]
@@ -153,7 +160,7 @@ def linear_wgrad_(dy, x, dw, db, relu_in=False, accumulate=False, defer=False):
     # r06: the wide grid-side products' weight gradients (the per-resolution sum matrices of the deferred update: N = 2368 ..
     # 2752 columns, K = 64 .. 256) on the split kernels -- fp32-grade products from three fp16 MFMAs like their forward and data
     # gradient (bx3_wgrad_kernel<.., GT = K / 32>; T2H_GEMM_BX3_WGRAD=1)
-    bx3 = (_GEMM_BX3_WGRAD and GEMM_BX3 and _MODE == "fp32" and not relu_in and n >= _BX3_WGRAD_MIN_N and m >= _BX3_WGRAD_MIN_M
+    bx3 = (row_limit is None and _GEMM_BX3_WGRAD and GEMM_BX3 and _MODE == "fp32" and not relu_in and n >= _BX3_WGRAD_MIN_N and m >= _BX3_WGRAD_MIN_M
            and _grid_h2() and bool(_lib.ws_bytes("t2h_gemm_bx3_wgrad_supported", m, k, n)))
     query, pflags = (("t2h_gemm_bx3_wgrad_workspace_bytes", _lib.F16X2) if bx3 else
                      ("t2h_linear_wgrad_workspace_bytes", (_lib.RELU_IN if relu_in else 0) | _pflag()))
@@ -165,6 +172,8 @@ def linear_wgrad_(dy, x, dw, db, relu_in=False, accumulate=False, defer=False):
     if bx3:
         _lib.call("t2h_gemm_bx3_wgrad", gp, ldg, xp, ldx, m, k, n, *outs, flags, ws.data_ptr(), ws_bytes, _lib.stream(), **cost)
     else:
+        if row_limit is not None:
+            _lib.compact_next(None, -1, row_limit)
         _lib.call("t2h_linear_wgrad", gp, ldg, xp, ldx, m, k, n, flags, *outs, ws.data_ptr(), ws_bytes, _lib.stream(), **cost)
 
 

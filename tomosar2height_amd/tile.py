@@ -195,6 +195,11 @@ class TileIndex:
             from . import ops, deferred
             if ops.SAMPLE_ADJOINT and 0 < tile.n_points <= ops.SAMPLE_ADJOINT_MAX_ROWS * tile.B * tile.R * tile.R:
                 tile.sample_adjoint(0)
+            # the row list of the level `Deferred` will compact, where that is known here: the default networks defer down to the
+            # tile's own resolution (level 0).  Another level is built on first use inside the step, with the same event behind it
+            from . import mlp
+            if deferred.COMPACT_SUMS and mlp._MODE == "fp32":
+                deferred.cell_rows(tile, 0)
             for lv in range(min(4, tile.nbits)):
                 deferred.counts(tile, lv)
                 if lv >= 1:
@@ -214,6 +219,7 @@ class TileIndex:
             else:
                 out += list(val)
         out += list(self.__dict__.get("_cell_counts", {}).values())
+        out += [buf for buf, _ in self.__dict__.get("_cell_rows", {}).values()]
         return out
 
     def wait_ready(self):
