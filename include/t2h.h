@@ -40,7 +40,7 @@ extern "C" {
 #define T2H_ERR_LAUNCH (-2)   /* HIP reported an error at launch */
 #define T2H_ERR_WORKSPACE (-3) /* workspace too small */
 
-#define T2H_ABI_VERSION 19
+#define T2H_ABI_VERSION 20
 #define T2H_MAX_NBITS 10      /* finest plane resolution up to 1024 */
 #define T2H_MAX_RAGGED_TILES 64 /* tiles per ragged batch (t2h_tile_build_ragged) */
 
@@ -166,12 +166,13 @@ int t2h_segmean_bwd(const float *gplane_nhwc, const int32_t *cell, const int32_t
  *   scatter_mean(c_k) = ( sum_j cellsum_r(h_j) A_{k,j}^T ) / count + const_k        (A_{k,j} = Wc_k .. Wc_{j+1} W1_j)
  * is formed on the r^2 pixels from per-cell sums of the hidden activations and c_k itself is never computed on the N points. */
 int t2h_segsum_fwd(const float *feat, const int32_t *off0, int B, int N, int nbits, int level, int C,
-                   float *plane_nhwc, int ld_plane, void *workspace, size_t workspace_bytes, t2h_stream_t stream);
+                   float *plane_nhwc, int ld_plane, void *workspace, size_t workspace_bytes, t2h_stream_t stream,
+                   const int32_t *row_of_cell);
 int t2h_plane_sumpool2x2(const float *fine_nhwc, int ld_fine, int B, int r_fine, int C, float *coarse_nhwc, int ld_coarse,
-                         t2h_stream_t stream);
+                         t2h_stream_t stream, const int32_t *fine_row_of_cell);
 int t2h_segsum_bwd_multi(const float *const *gplanes_nhwc, const int *levels, const int *lds, int n_planes, const int32_t *cell,
                          int B, int N, int nbits, int C, const float *mask, const float *addend, float *gfeat,
-                         t2h_stream_t stream);
+                         t2h_stream_t stream, const int32_t *row_of_cell, int rows_level);
 /* Row strides (`ld_*`, in floats, >= C): a plane may be a COLUMN BLOCK of a wider [B r r, K] matrix -- the per-cell sums of all
  * sources of the deferred form sit side by side per resolution, so that scatter_mean(c_k) is ONE product over K = sum K_j. */
 /* Grid-side glue of the deferred form (csrc/deferred.hip): the points-per-cell plane [B, r, r] (float, row-major) of an ALTO
@@ -183,24 +184,25 @@ int t2h_segsum_bwd_multi(const float *const *gplanes_nhwc, const int *levels, co
  * matching gradient row is never read, so the matrices of the finest deferred resolution hold one row per OCCUPIED cell: rows in
  * plane order within a tile, tile after tile.  They are allocated at B r r rows (the bound: no host ever reads the count).
  *
- * t2h_compact_next(row_of_cell, level, n_rows) is a request for the NEXT launch of the calling thread; the entry point that takes it
- * clears it, a launch that has no use for it ignores it.  The shapes of the existing calls do not change.
- *   - t2h_cell_counts with a request for ITS level also writes the level's row list into the caller's int32 buffer
- *       row_of_cell [P = B r r] (-1: empty cell) | cell_of_row [P] (first n_rows valid) | n_rows, 3 spare | ceil(P / 2048) scratch
- *     (n_rows must point at row_of_cell + 2 P);
- *   - t2h_segsum_fwd, t2h_sample_relu_cellsums_ordered (the `sums` output; `level` must be the sums' level) and the fine side of
- *     t2h_plane_sumpool2x2 address their plane through row_of_cell: an empty cell writes nothing / contributes 0;
- *   - t2h_segsum_bwd_multi and t2h_sample_bwd_from_sums_ordered read the plane whose level is `level` through row_of_cell;
+ * The entry points that touch such a matrix take its rows as their LAST argument(s), behind `stream`; NULL: one row per cell.  A
+ * launch acts on nothing but its own arguments.
+ *   - t2h_cell_counts with a `row_list` also writes its level's row list into that int32 buffer of the caller's,
+ *       row_of_cell [P = B r r] (-1: empty cell) | cell_of_row [P] (first n_rows valid) | n_rows, 3 spare | ceil(P / 2048) scratch;
+ *   - t2h_segsum_fwd (rows of `level`), t2h_sample_relu_cellsums_ordered (the `sums` output; rows of `sum_level`) and the fine side
+ *     of t2h_plane_sumpool2x2 address their plane through row_of_cell: an empty cell writes nothing / contributes 0;
+ *   - t2h_segsum_bwd_multi and t2h_sample_bwd_from_sums_ordered read the plane whose level is `rows_level` through row_of_cell
+ *     (T2H_ERR_ARG if no plane has that level; rows_level is not read when row_of_cell is NULL);
  *   - t2h_mean_bias_fwd reads acc[row_of_cell[p]] (an empty cell's output is 0 by a select), t2h_mean_bias_bwd writes
  *     dacc[row_of_cell[p]]; `cnt`, the output / `g` and the order of the column sums stay per cell;
  *   - t2h_gemm_bx3 returns from every row tile that starts at or behind *n_rows and stages the rows behind *n_rows of the last tile
- *     as zeros; t2h_linear_wgrad (fp32 kernel) sums over the first *n_rows rows only.  row_of_cell may be NULL for these. */
-void t2h_compact_next(const int32_t *row_of_cell, int level, const int32_t *n_rows);
-int t2h_cell_counts(const int32_t *off0, int B, int nbits, int level, float *cnt, t2h_stream_t stream);
-int t2h_mean_bias_fwd(const float *acc, const float *cnt, const float *cvec, int64_t P, int C, float *out, t2h_stream_t stream);
+ *     as zeros; t2h_linear_wgrad (fp32 kernel) sums over the first *n_rows rows only (`n_rows`: device int, the list's third part).
+ * t2h_sample_relu_cellsums, t2h_sample_relu_cellsums2 and t2h_sample_bwd_from_sums have no such argument: one row per cell. */
+int t2h_cell_counts(const int32_t *off0, int B, int nbits, int level, float *cnt, t2h_stream_t stream, int32_t *row_list);
+int t2h_mean_bias_fwd(const float *acc, const float *cnt, const float *cvec, int64_t P, int C, float *out, t2h_stream_t stream,
+                      const int32_t *row_of_cell);
 size_t t2h_mean_bias_bwd_workspace_bytes(int64_t P, int C);
 int t2h_mean_bias_bwd(const float *g, const float *cnt, int64_t P, int C, float *dacc, float *dcvec, void *workspace,
-                      size_t workspace_bytes, t2h_stream_t stream);
+                      size_t workspace_bytes, t2h_stream_t stream, const int32_t *row_of_cell);
 /* The forward of a deferred level at a coarse sampling resolution in ONE pass, with the hidden activations never leaving the
  * chip: per (cell of the sampling level, 256-channel chunk) one wave stages the cell's 3 x 3 pixel neighbourhood in LDS, walks the
  * cell's rows and emits the per-cell SUMS of relu(sample(plane)) at the finer resolution `sum_level` (into a column block with row
@@ -227,7 +229,8 @@ int t2h_cell_order_build_range(const int32_t *off0, int B, int nbits, int level_
                                t2h_stream_t stream);
 int t2h_sample_relu_cellsums_ordered(const float *plane_nhwc, const float *pts, int dim, const int32_t *off0, int B, int N,
                                      int nbits, int level, int sum_level, int C, float *sums_nhwc, int ld_sums, float *pooled_nhwc,
-                                     int ld_pooled, void *sign_bits, const int32_t *cell_order, t2h_stream_t stream);
+                                     int ld_pooled, void *sign_bits, const int32_t *cell_order, t2h_stream_t stream,
+                                     const int32_t *row_of_cell);
 /* t2h_segsum_bwd_multi folded into the sample adjoint's per-cell partial kernel: gplane [B, r, r, C] =
  * S^T ( (mask > 0) * sum_q gplanes_q[cell_q(.)] ) without the [N, C] hidden gradient ever being written.  Only where the level
  * takes the per-cell partials (t2h_sample_bwd_workspace_bytes > 0); same workspace.  `mask`: the hidden activations [N, C]
@@ -244,7 +247,8 @@ int t2h_sample_bwd_from_sums(const float *const *gplanes_nhwc, const int *levels
 int t2h_sample_bwd_from_sums_ordered(const float *const *gplanes_nhwc, const int *levels, const int *lds, int n_planes,
                                      const int32_t *cell, const void *mask, int mask_is_bits, const float *pts, int dim,
                                      const int32_t *off0, int B, int N, int nbits, int level, int C, float *gplane_nhwc,
-                                     void *workspace, size_t workspace_bytes, const int32_t *cell_order, t2h_stream_t stream);
+                                     void *workspace, size_t workspace_bytes, const int32_t *cell_order, t2h_stream_t stream,
+                                     const int32_t *row_of_cell, int rows_level);
 /* The same with `addend` [B*N, C] (may be NULL) added to the result: the point features of a level feed both the
  * rasterisation and the next level's fc_c (alto.py:123-130), so their gradient is a sum of two -- formed here instead of
  * by an extra elementwise pass (gfeat may alias addend). */
@@ -335,7 +339,7 @@ int t2h_linear_dgrad(const float *dy, int lddy, const float *w, float *dx, int l
                      const float *mask, int ldmask, int flags, t2h_stream_t stream);
 size_t t2h_linear_wgrad_workspace_bytes(int M, int K, int N);
 int t2h_linear_wgrad(const float *dy, int lddy, const float *x, int ldx, int M, int K, int N, int flags,
-                     float *dw, float *db, void *workspace, size_t workspace_bytes, t2h_stream_t stream);
+                     float *dw, float *db, void *workspace, size_t workspace_bytes, t2h_stream_t stream, const int32_t *n_rows);
 
 /* ---------------------------------------------------------------------------------------------
  * F.interpolate(size=(H, W), mode='bilinear', align_corners=True) pixel.py:107,110
@@ -454,13 +458,15 @@ int t2h_conv3x3_bx3_wgrad(const float *dy, const float *x, float *dw, float *db,
  * deferred ALTO point update (alto.py:123-130 re-associated, tomosar2height_amd/deferred.py), whose long reductions (K up to 2752
  * stacked columns) ran at 0.4-0.6 of the fp32 matrix peak.  W: [N][K] with row stride ldw (w_is_kn = 0, nn.Linear layout) or
  * [K][N] (w_is_kn = 1), split once by t2h_gemm_bx3_prepare.  M % 128 == 0, K % 64 == 0, N % 32 == 0 (t2h_gemm_bx3_supported);
- * ldx / ldy / ldm: row strides in floats (column slices of wider matrices are fine).  Few-row products split K into slabs. */
+ * ldx / ldy / ldm: row strides in floats (column slices of wider matrices are fine).  Few-row products split K into slabs.
+ * `n_rows` (may be NULL): rows in use of a compact per-cell matrix, see t2h_cell_counts. */
 int t2h_gemm_bx3_supported(int64_t M, int K, int N);
 size_t t2h_gemm_bx3_weights_bytes(int K, int N);
 int t2h_gemm_bx3_prepare(const float *w, int ldw, int K, int N, int w_is_kn, void *wf, t2h_stream_t stream);
 size_t t2h_gemm_bx3_workspace_bytes(int64_t M, int K, int N);
 int t2h_gemm_bx3(const float *x, int ldx, const void *wf, const float *bias, const float *mask, int ldm, float *y, int ldy,
-                 int64_t M, int K, int N, int flags, void *workspace, size_t workspace_bytes, t2h_stream_t stream);
+                 int64_t M, int K, int N, int flags, void *workspace, size_t workspace_bytes, t2h_stream_t stream,
+                 const int32_t *n_rows);
 
 /* r06: the weight gradient of the same product on the split kernels: dw [N, K] = [dw +] dy^T x, db [N] = [db +] colsum(dy) (db may be
  * NULL) -- the transposed product over the M rows (alto.py:123-130 re-associated: the Linear layers on pixel rows / per-cell sums;

@@ -26,7 +26,7 @@ def outs():
 order = tile.cell_order(level)
 def walk(o):
     _lib.call("t2h_sample_relu_cellsums_ordered", _lib.ptr(q), _lib.ptr(tile.pts), tile.dim, _lib.ptr(tile.off0), tile.B, tile.N, tile.nbits,
-              level, 0, C, o[0].data_ptr(), C, (o[1].data_ptr() if 'nopool' not in MODE else None), (C if 'nopool' not in MODE else 0), (o[2].data_ptr() if 'nobits' not in MODE else None), (_lib.ptr(order) if 'noorder' not in MODE else None), _lib.stream())
+              level, 0, C, o[0].data_ptr(), C, (o[1].data_ptr() if 'nopool' not in MODE else None), (C if 'nopool' not in MODE else 0), (o[2].data_ptr() if 'nobits' not in MODE else None), (_lib.ptr(order) if 'noorder' not in MODE else None), _lib.stream(), None)
 ref = outs(); walk(ref)
 res = [outs() for _ in range(4)]
 torch.cuda.synchronize()

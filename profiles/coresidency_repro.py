@@ -42,7 +42,7 @@ def outs():
 
 def walk(o):
     _lib.call("t2h_sample_relu_cellsums_ordered", _lib.ptr(q), _lib.ptr(tile.pts), tile.dim, _lib.ptr(tile.off0), tile.B, tile.N,
-              tile.nbits, level, 0, C, o[0].data_ptr(), C, o[1].data_ptr(), C, o[2].data_ptr(), _lib.ptr(order), _lib.stream())
+              tile.nbits, level, 0, C, o[0].data_ptr(), C, o[1].data_ptr(), C, o[2].data_ptr(), _lib.ptr(order), _lib.stream(), None)
 
 
 ref = outs()

@@ -26,7 +26,7 @@ def outs():
 order = tile.cell_order(level) if os.environ.get("NO_ORDER") != "1" else None
 def walk(o):
     _lib.call("t2h_sample_relu_cellsums_ordered", _lib.ptr(q), _lib.ptr(tile.pts), tile.dim, _lib.ptr(tile.off0), tile.B, tile.N, tile.nbits,
-              level, 0, C, o[0].data_ptr(), C, o[1].data_ptr(), C, o[2].data_ptr(), None if order is None else _lib.ptr(order), _lib.stream())
+              level, 0, C, o[0].data_ptr(), C, o[1].data_ptr(), C, o[2].data_ptr(), None if order is None else _lib.ptr(order), _lib.stream(), None)
 import ctypes
 lib = _lib.load()
 lib.t2h_debug_set.argtypes = [ctypes.c_void_p]

@@ -56,7 +56,7 @@ pooled = torch.empty(B * 128 * 128, 1024, device=dev)
 for _ in range(REPS):                                         # as deferred.py calls it: finest sums + the pooled ones, ordered
     _lib.call("t2h_sample_relu_cellsums_ordered", _lib.ptr(q), _lib.ptr(tile.pts), tile.dim, _lib.ptr(tile.off0), tile.B, tile.N,
               tile.nbits, lv32, 0, 1024, sums.data_ptr(), sums.stride(0), pooled.data_ptr(), pooled.stride(0), _lib.ptr(bits),
-              _lib.ptr(order), _lib.stream())
+              _lib.ptr(order), _lib.stream(), None)
 arr, lvs, lds = deferred._plane_args(grads)
 ws_bytes = _lib.ws_bytes("t2h_sample_bwd_workspace_bytes", tile.B, tile.N, tile.nbits, lv32, 1024)
 ws = _lib.workspace(ws_bytes, dev)
@@ -64,6 +64,6 @@ dq = torch.empty(B * 32 * 32, 1024, device=dev)
 for _ in range(REPS):
     _lib.call("t2h_sample_bwd_from_sums_ordered", arr, lvs, lds, len(grads), _lib.ptr(tile.cell), _lib.ptr(bits), 1, _lib.ptr(tile.pts),
               tile.dim, _lib.ptr(tile.off0), tile.B, tile.N, tile.nbits, lv32, 1024, _lib.ptr(dq), _lib.ptr(ws), ws_bytes,
-              _lib.ptr(order), _lib.stream())
+              _lib.ptr(order), _lib.stream(), None, -1)
 torch.cuda.synchronize()
 print("pmc_probe done")

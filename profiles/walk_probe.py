@@ -60,7 +60,7 @@ for c2, r in ((1024, 32), (512, 64), (256, 128)):
     def fwd():
         _lib.call("t2h_sample_relu_cellsums_ordered", _lib.ptr(q), _lib.ptr(tile.pts), tile.dim, _lib.ptr(tile.off0), tile.B, tile.N,
                   tile.nbits, lv, 0, c2, planes[0].data_ptr(), planes[0].stride(0), planes[1].data_ptr(), planes[1].stride(0),
-                  _lib.ptr(bits), _lib.ptr(order) if use_order[0] else None, _lib.stream())
+                  _lib.ptr(bits), _lib.ptr(order) if use_order[0] else None, _lib.stream(), None)
 
     ref = None
     for v in FWD:
@@ -86,7 +86,7 @@ for c2, r in ((1024, 32), (512, 64), (256, 128)):
     def bwd():
         _lib.call("t2h_sample_bwd_from_sums_ordered", arr, lvs, lds, len(grads), _lib.ptr(tile.cell), _lib.ptr(ref[2]), 1, _lib.ptr(tile.pts),
                   tile.dim, _lib.ptr(tile.off0), tile.B, tile.N, tile.nbits, lv, c2, _lib.ptr(dq), _lib.ptr(ws), ws_bytes,
-                  _lib.ptr(order) if use_order[0] else None, _lib.stream())
+                  _lib.ptr(order) if use_order[0] else None, _lib.stream(), None, -1)
 
     bref = None
     for v in BWD:

@@ -25,6 +25,24 @@ def test_library_exports_every_declared_symbol():
     assert lib.t2h_abi_version() == _lib.ABI_VERSION
 
 
+def test_no_launch_takes_its_rows_from_a_call_before_it():
+    """The compact rows of the per-cell matrices (include/t2h.h) are arguments of the launch that uses them: the entry point that
+    left a request for "the next launch of this thread" is gone from the library and the binding, and no source names it, its
+    thread-local or the function that took it."""
+    import glob
+    from tomosar2height_amd import _lib
+    lib = _lib.load()
+    assert not hasattr(lib, "t2h_compact_next") and not hasattr(_lib, "compact_next")
+    files = (glob.glob(os.path.join(ROOT, "tomosar2height_amd", "**", "*.py"), recursive=True)
+             + [f for f in glob.glob(os.path.join(ROOT, "tomosar2height_amd", "csrc", "*")) if os.path.isfile(f) and not f.endswith(".o")]
+             + glob.glob(os.path.join(ROOT, "include", "*.h")))
+    assert len(files) > 40
+    for f in files:
+        text = open(f, errors="replace").read()
+        for word in ("compact_next", "take_compact", "g_compact"):
+            assert word not in text, f"{os.path.relpath(f, ROOT)} names {word}"
+
+
 def test_host_side_helpers_need_no_gpu():
     from tomosar2height_amd import _lib
     lib = _lib.load()
@@ -47,7 +65,7 @@ def test_on_chip_cell_sums_refuse_the_one_pixel_level():
     nbits = 8
     args = (p, p, 3, p, 1, 10, nbits, nbits, 0, 256, p, 256)
     for name, tail in (("t2h_sample_relu_cellsums", (None, None)), ("t2h_sample_relu_cellsums2", (None, 0, None, None)),
-                       ("t2h_sample_relu_cellsums_ordered", (None, 0, None, None, None))):
+                       ("t2h_sample_relu_cellsums_ordered", (None, 0, None, None, None, None))):
         assert getattr(lib, name)(*args, *tail) == -1, name
         assert b"level < nbits" in lib.t2h_last_error_string(), name
 
@@ -122,17 +140,17 @@ def test_every_entry_point_rejects_bad_arguments_without_a_gpu():
         "t2h_segmean_fwd": (n, n, 1, 10, 8, 0, 32, n, n, 0, n),
         "t2h_segmean_bwd": (n, n, n, 1, 10, 8, 0, 32, n, n),
         "t2h_segmean_bwd_add": (n, n, n, 1, 10, 8, 0, 32, n, n, n),
-        "t2h_segsum_fwd": (n, n, 1, 10, 8, 0, 32, n, 32, n, 0, n),
-        "t2h_plane_sumpool2x2": (n, 32, 1, 32, 32, n, 32, n),
-        "t2h_segsum_bwd_multi": (n, n, n, 1, n, 1, 10, 8, 32, n, n, n, n),
-        "t2h_cell_counts": (n, 1, 8, 0, n, n),
-        "t2h_mean_bias_fwd": (n, n, n, 64, 32, n, n),
-        "t2h_mean_bias_bwd": (n, n, 64, 32, n, n, n, 0, n),
+        "t2h_segsum_fwd": (n, n, 1, 10, 8, 0, 32, n, 32, n, 0, n, n),
+        "t2h_plane_sumpool2x2": (n, 32, 1, 32, 32, n, 32, n, n),
+        "t2h_segsum_bwd_multi": (n, n, n, 1, n, 1, 10, 8, 32, n, n, n, n, n, -1),
+        "t2h_cell_counts": (n, 1, 8, 0, n, n, n),
+        "t2h_mean_bias_fwd": (n, n, n, 64, 32, n, n, n),
+        "t2h_mean_bias_bwd": (n, n, 64, 32, n, n, n, 0, n, n),
         "t2h_sample_relu_cellsums": (n, n, 3, n, 1, 10, 8, 2, 0, 256, n, 256, n, n),
         "t2h_sample_relu_cellsums2": (n, n, 3, n, 1, 10, 8, 2, 0, 256, n, 256, n, 256, n, n),
         "t2h_sample_bwd_from_sums": (n, n, n, 1, n, n, 0, n, 3, n, 1, 10, 8, 0, 32, n, n, 0, n),
-        "t2h_sample_bwd_from_sums_ordered": (n, n, n, 1, n, n, 0, n, 3, n, 1, 10, 8, 0, 32, n, n, 0, n, n),
-        "t2h_sample_relu_cellsums_ordered": (n, n, 3, n, 1, 10, 8, 2, 0, 256, n, 256, n, 256, n, n, n),
+        "t2h_sample_bwd_from_sums_ordered": (n, n, n, 1, n, n, 0, n, 3, n, 1, 10, 8, 0, 32, n, n, 0, n, n, n, -1),
+        "t2h_sample_relu_cellsums_ordered": (n, n, 3, n, 1, 10, 8, 2, 0, 256, n, 256, n, 256, n, n, n, n),
         "t2h_cell_order_build": (n, 1, 8, 2, n, n),
         "t2h_cell_order_build_range": (n, 1, 8, 1, 3, n, n),
         "t2h_sample_fwd": (n, n, 3, 1, 10, 32, 32, n, n),
@@ -145,7 +163,7 @@ def test_every_entry_point_rejects_bad_arguments_without_a_gpu():
         "t2h_linear_fwd": (n, 32, n, n, n, 32, 10, 32, 32, 0, n),
         "t2h_linear_fwd_add": (n, 32, n, n, n, 32, n, 32, 10, 32, 32, 0, n),
         "t2h_linear_dgrad": (n, 32, n, n, 32, 10, 32, 32, n, 0, 0, n),
-        "t2h_linear_wgrad": (n, 32, n, 32, 10, 32, 32, 0, n, n, n, 0, n),
+        "t2h_linear_wgrad": (n, 32, n, 32, 10, 32, 32, 0, n, n, n, 0, n, n),
         "t2h_upsample_bilinear_fwd": (n, n, 1, 32, 16, 16, 32, 32, n, n),
         "t2h_upsample_bilinear_bwd": (n, 1, 32, 16, 16, 32, 32, n, n),
         "t2h_upsample_bilinear_nhwc_fwd": (n, n, 1, 32, 16, 16, 32, 32, n, n),
@@ -181,7 +199,7 @@ def test_every_entry_point_rejects_bad_arguments_without_a_gpu():
         "t2h_split_weights_batch": (n, 1, n),
         "t2h_conv3x3_bx3_dgrad_rank1": (n, n, n, n, n, n, 1, 512, 512, 64, 128, 64, n),
         "t2h_gemm_bx3_wgrad": (n, 2752, n, 64, 128, 64, 2752, n, n, 64, n, 0, n),
-        "t2h_gemm_bx3": (n, 64, n, n, n, 0, n, 32, 128, 64, 32, 0, n, 0, n),
+        "t2h_gemm_bx3": (n, 64, n, n, n, 0, n, 32, 128, 64, 32, 0, n, 0, n, n),
         "t2h_upconv2x2_fwd": (n, n, n, n, 1, 32, 32, 32, 32, 0, n),
         "t2h_upconv2x2_fwd_add": (n, n, n, n, n, 1, 32, 32, 32, 32, 0, n),
         "t2h_upconv2x2_dgrad": (n, n, n, 1, 32, 32, 32, 32, 0, n, 0, n),

@@ -1,4 +1,4 @@
-"""-m gpu: the sum matrices of the finest deferred resolution by occupied row (T2H_COMPACT_SUMS, include/t2h.h: t2h_compact_next).
+"""-m gpu: the sum matrices of the finest deferred resolution by occupied row (T2H_COMPACT_SUMS, include/t2h.h: compact per-cell matrices).
 
   * the occupied-row list of a level (``deferred.cell_rows``) against a numpy restatement, exactly;
   * two deferred levels (r = 16, then r = 32 on a tile of R = 32; the r = 32 matrices are the compact ones) forward and backward with the
@@ -27,6 +27,11 @@ than a dense one: what lies downstream of a split product is NOT bit-identical b
     rest agrees to 4e-5 of the max-norm -- twice the 2e-5 that tests/test_hip_gemm.py allows one product against float64, each form being
     one split product away from exact.  Measured (printed): dQ 7.8e-8 and 1.6e-8, dbase 1.3e-10 in ``r64tiny``, 0 elsewhere (tiles of
     like-sized random numbers mostly share their power-of-two scale); weight gradients 1.7e-7 .. 3.8e-7.
+
+The rows are ARGUMENTS of the launch that uses them (the last ones, behind ``stream``), so a launch acts on nothing but its own:
+  * ``t2h_gemm_bx3`` / ``t2h_linear_wgrad`` with a row count, then the same call without: the second is the dense product, bit for bit;
+  * ``t2h_segsum_bwd_multi`` with the rows of a level that no plane has: refused before any launch;
+  * ``t2h_sample_relu_cellsums2`` (no such argument) right after a compact ``t2h_sample_relu_cellsums_ordered``: the dense layout.
 """
 import numpy as np
 import pytest
@@ -263,3 +268,94 @@ def test_split_products_stop_at_the_row_count(case, monkeypatch):
     e_dense, e_comp = _product_error(dense_products, None), _product_error(comp_products, n_rows)
     print(f"[compact] {case} x^T dacc: max error / sum |x . dacc|: dense {e_dense:.3e}, compact {e_comp:.3e}")
     assert e_comp <= 2.0 * e_dense
+
+
+# ---- the rows are arguments: a compact launch leaves nothing behind for the launch after it ----------------------------------------
+def _nan(*shape):
+    return torch.full(shape, float("nan"), device=_dev())
+
+
+def test_split_product_with_a_row_count_does_not_colour_the_next():
+    """t2h_gemm_bx3 at M = 256, K = 64, N = 32 (the smallest supported shape with a second 128-row tile): with n_rows -> 100 the
+    second tile is never written; the dense call right after it writes every row and equals the dense call made before, bit for bit."""
+    from tomosar2height_amd import mlp
+    g = torch.Generator().manual_seed(3)
+    x, w = torch.randn(256, 64, generator=g).to(_dev()), (torch.randn(32, 64, generator=g) / 8).to(_dev())
+    lim = torch.tensor([100], dtype=torch.int32, device=_dev())
+
+    def product(row_limit):
+        return mlp._gemm_bx3(x, w, False, None, None, _nan(256, 32), False, False, "t2h_linear_fwd[test]", row_limit)
+    before, compact, after = product(None), product(lim.data_ptr()), product(None)
+    torch.cuda.synchronize()
+    assert torch.isnan(compact[128:]).all() and torch.isfinite(compact[:100]).all()
+    assert torch.isfinite(before).all() and torch.isfinite(after).all()
+    assert torch.equal(after, before)
+
+
+def test_weight_gradient_with_a_row_count_does_not_colour_the_next():
+    """t2h_linear_wgrad over M = 256 rows (K = N = 32): with n_rows -> 100 it is the dense product of the first 100 rows, bit for
+    bit; the dense call right after it equals the dense call made before."""
+    from tomosar2height_amd import mlp
+    g = torch.Generator().manual_seed(4)
+    dy, x = torch.randn(256, 32, generator=g).to(_dev()), torch.randn(256, 32, generator=g).to(_dev())
+    lim = torch.tensor([100], dtype=torch.int32, device=_dev())
+
+    def product(dy, x, row_limit=None):
+        dw = _nan(32, 32)
+        mlp.linear_wgrad_(dy, x, dw, None, row_limit=row_limit)
+        return dw
+    before, compact, after = product(dy, x), product(dy, x, lim.data_ptr()), product(dy, x)
+    first100 = product(dy[:100], x[:100])
+    torch.cuda.synchronize()
+    assert torch.isfinite(before).all() and torch.isfinite(compact).all()
+    assert torch.equal(compact, first100) and not torch.equal(compact, before)
+    assert torch.equal(after, before)
+
+
+def test_rows_of_a_level_that_no_plane_has_are_refused():
+    """t2h_segsum_bwd_multi: a row list whose rows_level is none of levels[] is T2H_ERR_ARG, before any launch."""
+    from tomosar2height_amd import _lib, deferred
+    from tomosar2height_amd.tile import TileIndex
+    tile = TileIndex([_clustered(2100, 0).to(_dev())], 32)
+    c = 32
+    planes = [(torch.ones(tile.B * 1024, c, device=_dev()), 0), (torch.ones(tile.B * 256, c, device=_dev()), 1)]
+    arr, lvs, lds = deferred._plane_args(planes)
+    rows = deferred.cell_rows(tile, 0)
+    out = _nan(tile.n_points, c)
+    with pytest.raises(_lib.T2HLibraryError, match=r"t2h_segsum_bwd_multi failed \(code -1\).*level 2"):
+        _lib.call("t2h_segsum_bwd_multi", arr, lvs, lds, len(planes), _lib.ptr(tile.cell), tile.B, tile.N, tile.nbits, c, None, None,
+                  _lib.ptr(out), _lib.stream(), rows.data_ptr(), 2)
+    torch.cuda.synchronize()
+    assert torch.isnan(out).all()
+
+
+def test_dense_cell_sums_right_after_compact_ones():
+    """t2h_sample_relu_cellsums2 takes no rows: right after a t2h_sample_relu_cellsums_ordered that wrote its sums by occupied row
+    (R = 32, sampling level r = 16, sums at r = 32, C = 256) it writes one row per cell, the same bits as when called first."""
+    from tomosar2height_amd import _lib, deferred
+    from tomosar2height_amd.tile import TileIndex
+    clouds = [_clustered(2100, 0)]
+    tile = TileIndex([cl.to(_dev()) for cl in clouds], 32)
+    c, lv = 256, 1
+    q = torch.randn(tile.B, 16, 16, c, generator=torch.Generator().manual_seed(9)).to(_dev())
+    head = (_lib.ptr(q), _lib.ptr(tile.pts), tile.dim, _lib.ptr(tile.off0), tile.B, tile.N, tile.nbits, lv, 0, c)
+
+    def dense():
+        sums, pooled = _nan(tile.B * 1024, c), _nan(tile.B * 256, c)
+        _lib.call("t2h_sample_relu_cellsums2", *head, _lib.ptr(sums), c, _lib.ptr(pooled), c, None, _lib.stream())
+        return sums, pooled
+    first = dense()
+    rows = deferred.cell_rows(tile, 0)
+    by_row, pooled = _nan(tile.B * 1024, c), _nan(tile.B * 256, c)
+    _lib.call("t2h_sample_relu_cellsums_ordered", *head, _lib.ptr(by_row), c, _lib.ptr(pooled), c, None, None, _lib.stream(),
+              rows.data_ptr())
+    again = dense()
+    torch.cuda.synchronize()
+    row_of_cell, cell_of_row = _rows_ref(clouds, 32)
+    n_rows = len(cell_of_row)
+    assert 0 < n_rows < 1024
+    assert torch.isnan(by_row[n_rows:]).all()                                        # (the launch in between was a compact one)
+    assert torch.equal(by_row[:n_rows], first[0][torch.from_numpy(cell_of_row).long().to(_dev())])
+    assert torch.equal(pooled, first[1])
+    for a, b in zip(again, first):
+        assert torch.isfinite(a).all() and torch.equal(a, b)

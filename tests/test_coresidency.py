@@ -54,7 +54,7 @@ def test_walks_beside_the_split_convolutions_are_bit_identical():
 
         def walk(o, level=level, c=c, q=q, order=order):
             _lib.call("t2h_sample_relu_cellsums_ordered", _lib.ptr(q), _lib.ptr(tile.pts), tile.dim, _lib.ptr(tile.off0), tile.B, tile.N,
-                      tile.nbits, level, 0, c, o[0].data_ptr(), c, o[1].data_ptr(), c, o[2].data_ptr(), _lib.ptr(order), _lib.stream())
+                      tile.nbits, level, 0, c, o[0].data_ptr(), c, o[1].data_ptr(), c, o[2].data_ptr(), _lib.ptr(order), _lib.stream(), None)
         ref = outs()
         walk(ref)
         cases.append((f"forward walk level {level}", walk, ref, [outs() for _ in range(4)]))

@@ -49,7 +49,7 @@ def test_eval_header_matches_signatures_and_library():
     assert not any("eval" in name for name in declared_symbols("t2h.h"))
     assert not any(name.startswith("t2h_eval") for name in _lib.SIGNATURES)
     assert sorted(_lib.SIGNATURES) == declared_symbols("t2h.h")
-    assert _lib.ABI_VERSION == 19 == lib.t2h_abi_version()
+    assert _lib.ABI_VERSION == 20 == lib.t2h_abi_version()
 
 
 def test_eval_entries_reject_bad_arguments_without_a_gpu():

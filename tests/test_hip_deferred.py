@@ -162,13 +162,13 @@ def test_mean_bias_forward_and_backward():
     cnt = torch.randint(0, 4, (p,), generator=g).float().to(_dev())
     from tomosar2height_amd import _lib
     out = torch.empty(p, c, device=_dev())
-    _lib.call("t2h_mean_bias_fwd", _lib.ptr(acc.detach()), _lib.ptr(cnt), _lib.ptr(const.detach()), p, c, _lib.ptr(out), _lib.stream())
+    _lib.call("t2h_mean_bias_fwd", _lib.ptr(acc.detach()), _lib.ptr(cnt), _lib.ptr(const.detach()), p, c, _lib.ptr(out), _lib.stream(), None)
     up = torch.randn(p, c, generator=g).to(_dev())
     dacc, dconst = torch.empty(p, c, device=_dev()), torch.empty(1, c, device=_dev())
     ws_bytes = _lib.load().t2h_mean_bias_bwd_workspace_bytes(p, c)
     ws = _lib.workspace(ws_bytes, _dev())
     _lib.call("t2h_mean_bias_bwd", _lib.ptr(up), _lib.ptr(cnt), p, c, _lib.ptr(dacc), _lib.ptr(dconst), _lib.ptr(ws), ws_bytes,
-              _lib.stream())
+              _lib.stream(), None)
     a64, c64 = acc.detach().to(D).requires_grad_(True), const.detach().to(D).requires_grad_(True)
     want = a64 / cnt.to(D).clamp_min(1.0)[:, None] + (cnt > 0).to(D)[:, None] * c64
     assert ((out.to(D) - want).abs().max() / want.abs().max()).item() <= 1e-6
@@ -271,7 +271,7 @@ def test_cell_order_is_longest_first_and_changes_no_bit(c, r, sum_level, batch):
         bits = torch.zeros(tile.n_points * (c // 256) * 4, dtype=torch.int64, device=_dev())
         _lib.call("t2h_sample_relu_cellsums_ordered", _lib.ptr(q), _lib.ptr(tile.pts), tile.dim, _lib.ptr(tile.off0), tile.B,
                   tile.N, tile.nbits, lv, sum_level, c, _lib.ptr(sums), c, _lib.ptr(pooled) if sum_level < lv else None, c,
-                  _lib.ptr(bits), None if order_arg is None else _lib.ptr(order_arg), _lib.stream())
+                  _lib.ptr(bits), None if order_arg is None else _lib.ptr(order_arg), _lib.stream(), None)
         return sums, pooled, bits
 
     ref = forward(None)
@@ -306,6 +306,6 @@ def test_cell_order_is_longest_first_and_changes_no_bit(c, r, sum_level, batch):
         dq = torch.full((tile.B * r * r, c), float("nan"), device=_dev())
         _lib.call("t2h_sample_bwd_from_sums_ordered", arr, lvs, lds, len(planes), _lib.ptr(tile.cell), _lib.ptr(ref[2]), 1,
                   _lib.ptr(tile.pts), tile.dim, _lib.ptr(tile.off0), tile.B, tile.N, tile.nbits, lv, c, _lib.ptr(dq), _lib.ptr(ws),
-                  ws_bytes, None if o is None else _lib.ptr(o), _lib.stream())
+                  ws_bytes, None if o is None else _lib.ptr(o), _lib.stream(), None, -1)
         outs.append(dq)
     assert torch.equal(outs[0], outs[1]) and torch.equal(outs[1], outs[2]) and bool(torch.isfinite(outs[0]).all())

@@ -77,7 +77,7 @@ def test_inst_header_matches_signatures_and_library():
     for header in ("t2h.h", "t2h_eval.h"):
         assert not any("t2h_inst" in name for name in declared_symbols(header))
     assert not any("t2h_inst" in name for name in list(_lib.SIGNATURES) + list(evaluator.SIGNATURES))
-    assert _lib.ABI_VERSION == 19 == lib.t2h_abi_version()
+    assert _lib.ABI_VERSION == 20 == lib.t2h_abi_version()
     text = open(_lib.os.path.join(_lib.os.path.dirname(_lib._HERE), "include", "t2h_inst.h")).read()
     for name, value in (("TILE", instances.TILE), ("TINY_MAX", instances.TINY_MAX), ("SMALL_MAX", instances.SMALL_MAX),
                         ("TABLE_COLS", instances.TABLE_COLS)):

@@ -78,7 +78,7 @@ def test_interp_header_matches_signatures_and_library():
         assert not any("t2h_interp" in name for name in declared_symbols(header))
     others = list(_lib.SIGNATURES) + list(evaluator.SIGNATURES) + list(instances.SIGNATURES)
     assert not any("t2h_interp" in name for name in others)
-    assert _lib.ABI_VERSION == 19 == lib.t2h_abi_version()
+    assert _lib.ABI_VERSION == 20 == lib.t2h_abi_version()
     assert any(h.endswith("t2h_interp.h") for h in build.PUBLIC_HEADERS)
     text = open(_lib.os.path.join(_lib.os.path.dirname(_lib._HERE), "include", "t2h_interp.h")).read()
     for name, value in (("TILE", interpolate.TILE), ("CHUNK", interpolate.CHUNK), ("MAX_K", interpolate.MAX_K),

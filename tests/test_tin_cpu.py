@@ -101,7 +101,7 @@ def test_tin_header_matches_signatures_and_library():
     others = (list(_lib.SIGNATURES) + list(evaluator.SIGNATURES) + list(instances.SIGNATURES) + list(interpolate.SIGNATURES) +
               list(cloud_instances.SIGNATURES))
     assert not any("t2h_tin" in name for name in others)
-    assert _lib.ABI_VERSION == 19 == lib.t2h_abi_version()
+    assert _lib.ABI_VERSION == 20 == lib.t2h_abi_version()
     assert any(h.endswith("t2h_tin.h") for h in build.PUBLIC_HEADERS)
     assert any(s.endswith("dsm_tin.hip") for s in build.sources())
     text = open(_lib.os.path.join(_lib.os.path.dirname(_lib._HERE), "include", "t2h_tin.h")).read()

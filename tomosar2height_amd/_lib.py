@@ -19,7 +19,7 @@ import torch  # noqa: F401  (must precede the CDLL below, see docstring)
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # T2H_LIBRARY: load another build of the same ABI (A/B runs of a kernel change; a site-specific install path)
 LIB_PATH = os.environ.get("T2H_LIBRARY") or os.path.join(_HERE, "libt2h_hip.so")
-ABI_VERSION = 19
+ABI_VERSION = 20
 
 _vp, _i, _i64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t
 
@@ -30,7 +30,6 @@ SIGNATURES = {
     "t2h_last_kernel_name": (ctypes.c_char_p, []),
     "t2h_clear_kernel_name": (None, []),
     "t2h_debug_poison_lds": (_i, [_vp]),
-    "t2h_compact_next": (None, [_vp, _i, _vp]),
     "t2h_coordinate2index": (_i, [_vp, _i, _i64, _i, _vp, _vp]),
     "t2h_tile_workspace_bytes": (_sz, [_i, _i, _i]),
     "t2h_tile_build": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
@@ -48,21 +47,21 @@ SIGNATURES = {
     "t2h_segmean_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "t2h_segmean_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "t2h_segmean_bwd_add": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "t2h_segsum_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _sz, _vp]),
-    "t2h_plane_sumpool2x2": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp]),
-    "t2h_segsum_bwd_multi": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
-    "t2h_cell_counts": (_i, [_vp, _i, _i, _i, _vp, _vp]),
-    "t2h_mean_bias_fwd": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp]),
+    "t2h_segsum_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _i, _vp, _sz, _vp, _vp]),
+    "t2h_plane_sumpool2x2": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
+    "t2h_segsum_bwd_multi": (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i]),
+    "t2h_cell_counts": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp]),
+    "t2h_mean_bias_fwd": (_i, [_vp, _vp, _vp, _i64, _i, _vp, _vp, _vp]),
     "t2h_mean_bias_bwd_workspace_bytes": (_sz, [_i64, _i]),
-    "t2h_mean_bias_bwd": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _sz, _vp]),
+    "t2h_mean_bias_bwd": (_i, [_vp, _vp, _i64, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
     "t2h_sample_relu_cellsums": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _vp]),
     "t2h_sample_relu_cellsums2": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp]),
     "t2h_cell_order_len": (_sz, [_i, _i, _i]),
     "t2h_cell_order_build": (_i, [_vp, _i, _i, _i, _vp, _vp]),
     "t2h_cell_order_build_range": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
-    "t2h_sample_relu_cellsums_ordered": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "t2h_sample_relu_cellsums_ordered": (_i, [_vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _vp, _vp, _vp, _vp]),
     "t2h_sample_bwd_from_sums": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    "t2h_sample_bwd_from_sums_ordered": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _vp]),
+    "t2h_sample_bwd_from_sums_ordered": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp, _vp, _vp, _i]),
     "t2h_sample_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "t2h_sample_fwd_relu": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "t2h_sample_bwd_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
@@ -76,7 +75,7 @@ SIGNATURES = {
     "t2h_linear_fwd_add": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _i, _vp]),
     "t2h_linear_dgrad": (_i, [_vp, _i, _vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "t2h_linear_wgrad_workspace_bytes": (_sz, [_i, _i, _i]),
-    "t2h_linear_wgrad": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "t2h_linear_wgrad": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp, _vp]),
     "t2h_upsample_bilinear_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "t2h_upsample_bilinear_bwd": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "t2h_bias_relu_fwd": (_i, [_vp, _vp, _i64, _i, _i, _vp]),
@@ -125,7 +124,7 @@ SIGNATURES = {
     "t2h_gemm_bx3_wgrad_supported": (_i, [_i64, _i, _i]),
     "t2h_gemm_bx3_wgrad_workspace_bytes": (_sz, [_i64, _i, _i]),
     "t2h_gemm_bx3_wgrad": (_i, [_vp, _i, _vp, _i, _i64, _i, _i, _vp, _vp, _i, _vp, _sz, _vp]),
-    "t2h_gemm_bx3": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i64, _i, _i, _i, _vp, _sz, _vp]),
+    "t2h_gemm_bx3": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _i, _i64, _i, _i, _i, _vp, _sz, _vp, _vp]),
     "t2h_reduce_capture_begin": (_i, []),
     "t2h_reduce_capture_pending": (_i, []),
     "t2h_reduce_capture_end": (_i, [_vp]),
@@ -333,7 +332,7 @@ def load():
 def check(rc: int, what: str):
     if rc != 0:
         msg = load().t2h_last_error_string().decode(errors="replace")
-        raise RuntimeError(f"{what} failed (code {rc}): {msg}")
+        raise T2HLibraryError(f"{what} failed (code {rc}): {msg}")
 
 
 class KernelTimeline:
@@ -415,13 +414,6 @@ def call(name: str, *args, nbytes: int = 0, flops: int = 0, tag: str = None):
         symbol = lib.t2h_last_kernel_name().decode() or name
         tl.records.append((tag or name, nbytes, flops, s, e, symbol))
     check(rc, name)
-
-
-def compact_next(row_of_cell, level: int, n_rows):
-    """``t2h_compact_next`` (include/t2h.h): the NEXT launch of this thread addresses the per-cell matrix of ALTO level ``level``
-    by occupied row (``row_of_cell``: device pointer or None) and / or stops at ``*n_rows`` rows (device pointer or None).  Call it
-    right before the ``call`` it is meant for: that entry point takes the request and clears it."""
-    load().t2h_compact_next(row_of_cell, level, n_rows)
 
 
 def ptr(t: torch.Tensor) -> int:

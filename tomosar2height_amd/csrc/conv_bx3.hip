@@ -268,7 +268,7 @@ struct RowsArgs {
     // a decoder activation's gradient (pixel.py:31: conv4(cat[x, x1, x2, x3])), formed in this epilogue instead of being written by
     // the head's backward and read back here as "old values" (T2H_ACCUM): same products, same order of additions, same bits
     const float *r1_g, *r1_w;
-    // plain 1-tap (GEMM) form on a compact matrix (t2h_compact_next): device int, the rows in use.  A workgroup whose first row lies
+    // plain 1-tap (GEMM) form on a compact matrix (T2H_COMPACT_SUMS): device int, the rows in use.  A workgroup whose first row lies
     // behind them returns; the last partial tile stages the rows behind them as ZEROS (they are uninitialised memory, and a staged
     // value takes part in the tile's fp16 block scale), and what it computes for them nobody reads
     const int *row_limit;
@@ -1266,8 +1266,8 @@ T2H_API size_t t2h_gemm_bx3_workspace_bytes(int64_t M, int K, int N) {
 }
 
 T2H_API int t2h_gemm_bx3(const float *x, int ldx, const void *wf, const float *bias, const float *mask, int ldm, float *y, int ldy,
-                         int64_t M, int K, int N, int flags, void *workspace, size_t workspace_bytes, t2h_stream_t stream) {
-    const CompactRows cr = take_compact();
+                         int64_t M, int K, int N, int flags, void *workspace, size_t workspace_bytes, t2h_stream_t stream,
+                         const int32_t *n_rows) {
     if (!x || !wf || !y) return fail(T2H_ERR_ARG, "gemm_bx3: null pointer");
     if (!t2h_gemm_bx3_supported(M, K, N))
         return fail(T2H_ERR_ARG, "gemm_bx3: needs M %% 128 == 0, K %% 64 == 0, N %% 32 == 0 (M=%lld K=%d N=%d)", (long long)M, K, N);
@@ -1279,7 +1279,7 @@ T2H_API int t2h_gemm_bx3(const float *x, int ldx, const void *wf, const float *b
     a.B = 1; a.H = (int)(M / 32); a.W = 32; a.Kc = K; a.Nc = N; a.ldx = ldx; a.ldy = ldy; a.ldm = ldm;
     a.flags = ((flags & T2H_RELU_OUT) ? F_RELU_OUT : 0) | ((flags & T2H_ACCUM) ? F_ACCUM : 0);
     a.wscale = f16_trailer(wf, (size_t)K * N * 4);
-    a.row_limit = cr.n_rows;
+    a.row_limit = n_rows;
     return launch_rows(a, npl_of(flags), workspace, workspace_bytes, as_stream(stream), "gemm_bx3", 1);
 }
 

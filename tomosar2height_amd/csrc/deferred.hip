@@ -24,7 +24,7 @@ __global__ __launch_bounds__(256) void cell_counts_kernel(const int32_t *__restr
     cnt[i] = (float)(off0[obase + ((size_t)1 << (2 * level))] - off0[obase]);
 }
 
-// ---- occupied-row list of a level (t2h_compact_next + t2h_cell_counts): the occupied cells in plane order, tile after tile, get the
+// ---- occupied-row list of a level (t2h_cell_counts with a row_list): the occupied cells in plane order, tile after tile, get the
 // rows 0 .. n_rows - 1.  Three passes over 2048-cell blocks: occupied cells per block, an exclusive scan of the block counts by one
 // workgroup (which also leaves n_rows), then every block ranks its own cells behind its base.  Integer work in a fixed order.
 constexpr int kRowBlock = 2048;                                       // cells per workgroup: 256 threads x 8 consecutive cells
@@ -96,7 +96,7 @@ __global__ __launch_bounds__(256) void cell_rows_fill_kernel(const int32_t *__re
         }
 }
 
-// rows (optional, t2h_compact_next): acc holds one row per OCCUPIED cell, rows[p] = the row of cell p or -1.  An empty cell's output
+// rows (optional, T2H_COMPACT_SUMS): acc holds one row per OCCUPIED cell, rows[p] = the row of cell p or -1.  An empty cell's output
 // is 0 by a select, not by a product: the rows past n_rows are uninitialised memory (and an empty cell has no row to read at all)
 __global__ __launch_bounds__(256) void mean_bias_fwd_kernel(const float *__restrict__ acc, const float *__restrict__ cnt,
                                                            const float *__restrict__ cvec, int64_t total4, int C4,
@@ -145,7 +145,7 @@ __global__ __launch_bounds__(256) void mean_bias_bwd_kernel(const float *__restr
             for (int i = slot; i < rows; i += slots) {
                 const float n = cnt[p0 + i];
                 const float4 v = reinterpret_cast<const float4 *>(g + (size_t)(p0 + i) * C)[c4];
-                // rowmap (t2h_compact_next): dacc holds one row per occupied cell; the cells are still visited in plane order, so
+                // rowmap (T2H_COMPACT_SUMS): dacc holds one row per occupied cell; the cells are still visited in plane order, so
                 // the column sums below keep their summation order
                 const int64_t drow = rowmap ? (n > 0.f ? (int64_t)rowmap[p0 + i] : -1) : p0 + i;
                 if (dacc && drow >= 0) {
@@ -175,19 +175,16 @@ __global__ __launch_bounds__(256) void mean_bias_bwd_kernel(const float *__restr
 
 using namespace t2h;
 
-T2H_API int t2h_cell_counts(const int32_t *off0, int B, int nbits, int level, float *cnt, t2h_stream_t stream) {
-    const CompactRows rows = take_compact();
+T2H_API int t2h_cell_counts(const int32_t *off0, int B, int nbits, int level, float *cnt, t2h_stream_t stream, int32_t *row_list) {
     if (!off0 || !cnt) return fail(T2H_ERR_ARG, "cell_counts: null pointer");
     if (B < 1 || nbits < 1 || nbits > T2H_MAX_NBITS || level < 0 || level > nbits) return fail(T2H_ERR_ARG, "cell_counts: bad level");
     const int64_t total = (int64_t)B << (2 * (nbits - level));
     hipLaunchKernelGGL(cell_counts_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, as_stream(stream), off0, B, nbits,
                        level, cnt);
     if (int rc = check_launch("cell_counts")) return rc;
-    if (!rows.row_of_cell) return T2H_OK;
-    // the level's occupied-row list too (include/t2h.h, t2h_compact_next): [row_of_cell P | cell_of_row P | n_rows, 3 spare | scratch]
-    if (rows.level != level || !rows.n_rows || rows.n_rows != rows.row_of_cell + 2 * total)
-        return fail(T2H_ERR_ARG, "cell_counts: the row list asked for is not this level's (level %d, asked %d)", level, rows.level);
-    int32_t *row_of_cell = const_cast<int32_t *>(rows.row_of_cell), *n_rows = const_cast<int32_t *>(rows.n_rows);
+    if (!row_list) return T2H_OK;
+    // the level's occupied-row list too (include/t2h.h, compact per-cell matrices): [row_of_cell P | cell_of_row P | n_rows, 3 spare | scratch]
+    int32_t *row_of_cell = row_list, *n_rows = row_list + 2 * total;
     int32_t *blockcnt = n_rows + 4;
     const int nblk = (int)((total + kRowBlock - 1) / kRowBlock);
     hipLaunchKernelGGL(cell_rows_count_kernel, dim3(nblk), dim3(256), 0, as_stream(stream), off0, nbits, level, total, blockcnt);
@@ -200,15 +197,14 @@ T2H_API int t2h_cell_counts(const int32_t *off0, int B, int nbits, int level, fl
 static bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 
 T2H_API int t2h_mean_bias_fwd(const float *acc, const float *cnt, const float *cvec, int64_t P, int C, float *out,
-                              t2h_stream_t stream) {
-    const CompactRows rows = take_compact();
+                              t2h_stream_t stream, const int32_t *row_of_cell) {
     if (!acc || !cnt || !cvec || !out) return fail(T2H_ERR_ARG, "mean_bias_fwd: null pointer");
     if (P < 0 || C < 4 || C % 4 != 0 || !al16(acc) || !al16(cvec) || !al16(out))
         return fail(T2H_ERR_ARG, "mean_bias_fwd: needs C %% 4 == 0 and 16-byte aligned rows");
     if (P == 0) return T2H_OK;
     const int64_t total4 = P * (C / 4);
     hipLaunchKernelGGL(mean_bias_fwd_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, as_stream(stream), acc, cnt,
-                       cvec, total4, C / 4, out, rows.row_of_cell);
+                       cvec, total4, C / 4, out, row_of_cell);
     return check_launch("mean_bias_fwd");
 }
 
@@ -219,8 +215,7 @@ T2H_API size_t t2h_mean_bias_bwd_workspace_bytes(int64_t P, int C) {
 }
 
 T2H_API int t2h_mean_bias_bwd(const float *g, const float *cnt, int64_t P, int C, float *dacc, float *dcvec, void *workspace,
-                              size_t workspace_bytes, t2h_stream_t stream) {
-    const CompactRows rows = take_compact();
+                              size_t workspace_bytes, t2h_stream_t stream, const int32_t *row_of_cell) {
     if (!g || !cnt) return fail(T2H_ERR_ARG, "mean_bias_bwd: null pointer");
     if (P < 1 || C < 4 || C % 4 != 0 || !al16(g) || (dacc && !al16(dacc)) || (dcvec && !al16(dcvec)))
         return fail(T2H_ERR_ARG, "mean_bias_bwd: needs P >= 1, C %% 4 == 0 and 16-byte aligned rows");
@@ -232,7 +227,7 @@ T2H_API int t2h_mean_bias_bwd(const float *g, const float *cnt, int64_t P, int C
     const int blocks = (int)((P + kMbRows - 1) / kMbRows);
     float *slab = dcvec ? static_cast<float *>(workspace) : nullptr;
     hipLaunchKernelGGL(mean_bias_bwd_kernel, dim3(blocks), dim3(256), 0, as_stream(stream), g, cnt, P, C, dacc, slab, kMbRows,
-                       rows.row_of_cell);
+                       row_of_cell);
     if (int rc = check_launch("mean_bias_bwd")) return rc;
     if (!dcvec) return T2H_OK;
     return launch_reduce_slabs(slab, blocks, C, 1, C, C, 0, dcvec, nullptr, nullptr, as_stream(stream));

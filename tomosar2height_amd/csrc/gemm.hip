@@ -753,8 +753,8 @@ T2H_API size_t t2h_linear_wgrad_workspace_bytes(int M, int K, int N) {
 }
 
 T2H_API int t2h_linear_wgrad(const float *dy, int lddy, const float *x, int ldx, int M, int K, int N, int flags,
-                             float *dw, float *db, void *workspace, size_t workspace_bytes, t2h_stream_t stream) {
-    const CompactRows cr = take_compact();
+                             float *dw, float *db, void *workspace, size_t workspace_bytes, t2h_stream_t stream,
+                             const int32_t *n_rows) {
     if (!dy || !x || !dw) return fail(T2H_ERR_ARG, "linear_wgrad: null pointer");
     if (M < 1 || K < 1 || N < 1 || lddy < N || ldx < K) return fail(T2H_ERR_ARG, "linear_wgrad: bad shape");
     size_t need = t2h_linear_wgrad_workspace_bytes(M, K, N);
@@ -769,7 +769,7 @@ T2H_API int t2h_linear_wgrad(const float *dy, int lddy, const float *x, int ldx,
     // itself and the slab reduction launch is skipped (same values: the reduction of one slab is a copy)
     const bool direct = !p.smallk && p.splits == 1 && !accumulate && !db && aligned4(dw, K);
     if (direct) slab = dw;
-    if (p.smallk && cr.n_rows) return fail(T2H_ERR_ARG, "linear_wgrad: a row limit needs K %% 4 == 0");
+    if (p.smallk && n_rows) return fail(T2H_ERR_ARG, "linear_wgrad: a row limit needs K %% 4 == 0");
     if (p.smallk) {
         if (K > kSmallKMax) return fail(T2H_ERR_ARG, "linear_wgrad: K=%d must be a multiple of 4 (or <= %d)", K, kSmallKMax);
         hipLaunchKernelGGL(wgrad_smallk_kernel, dim3(p.splits), dim3(256), 0, s, dy, lddy, x, ldx, M, K, N,
@@ -782,7 +782,7 @@ T2H_API int t2h_linear_wgrad(const float *dy, int lddy, const float *x, int ldx,
         a.A = dy; a.lda = lddy; a.B = x; a.ldb = ldx; a.C = slab; a.ldc = K; a.colsum = db ? colslab : nullptr;
         a.M = N; a.N = K; a.K = M; a.flags = (flags & T2H_RELU_IN) ? F_RELU_B : 0;
         a.k_chunk = p.k_chunk; a.slab_stride = (long long)N * K;
-        a.k_limit = cr.n_rows;                 // (only gemm_kernel reads it: with a limit the other TN forms below are not taken)
+        a.k_limit = n_rows;                    // (only gemm_kernel reads it: with a limit the other TN forms below are not taken)
         int rc;
         const int mode = mode_of(flags);
         // the grid-side products of the deferred point update at r = 32 (1024 pixel rows, no bias gradient; 4096 rows and more: the

@@ -19,7 +19,7 @@ struct GemmArgs {
     int flags;
     int k_chunk;           // reduction range per split
     long long slab_stride; // C offset per split (floats)
-    // TN (weight gradient) on a compact matrix (t2h_compact_next): device int, the reduction stops at min(K, *k_limit) rows.  The
+    // TN (weight gradient) on a compact matrix (T2H_COMPACT_SUMS): device int, the reduction stops at min(K, *k_limit) rows.  The
     // rows behind it are uninitialised memory and must count as zero: the loader's `k < kend` mask does that -- nothing is cleared
     const int *k_limit;
 };

@@ -393,7 +393,7 @@ __global__ __launch_bounds__(kThreads) void segmean_fwd_kernel(const float *__re
     int cx = (int)compact1by1(mk), cy = (int)compact1by1(mk >> 1);
     int r = 1 << rbits;
     int64_t orow_i = ((int64_t)b * r + cy) * r + cx;
-    if (rowmap) {                         // compact rows (t2h_compact_next): an empty cell has no row and writes nothing
+    if (rowmap) {                         // compact rows (T2H_COMPACT_SUMS): an empty cell has no row and writes nothing
         if (e <= s) return;
         orow_i = rowmap[orow_i];
     }
@@ -430,7 +430,7 @@ __global__ __launch_bounds__(kThreads) void segmean_fwd_kernel(const float *__re
 constexpr int kMaxMultiPlanes = 8;
 struct MultiPlanes {
     const float *g[kMaxMultiPlanes]; int level[kMaxMultiPlanes]; int ld[kMaxMultiPlanes]; int n;
-    // compact rows (t2h_compact_next): plane `cq` (-1: none) holds one row per OCCUPIED cell, rowmap[cell in plane order] = its row,
+    // compact rows (T2H_COMPACT_SUMS): plane `cq` (-1: none) holds one row per OCCUPIED cell, rowmap[cell in plane order] = its row,
     // -1 for an empty cell; `cells`: entries of rowmap
     int cq = -1; const int32_t *rowmap = nullptr; int cells = 0;
 };
@@ -440,11 +440,13 @@ __device__ inline int plane_row(const MultiPlanes &mp, int q, int ci) {
     if (q == mp.cq) ci = mp.rowmap[ci];
     return ci;
 }
-static void set_compact(MultiPlanes &mp, const CompactRows &cr, int B, int nbits) {
+// the plane of level `rows_level` is the compact one; false: row_of_cell given, but no plane has that level
+static bool set_compact(MultiPlanes &mp, const int32_t *row_of_cell, int rows_level, int B, int nbits) {
     mp.cq = -1; mp.rowmap = nullptr; mp.cells = 0;
-    if (!cr.row_of_cell) return;
+    if (!row_of_cell) return true;
     for (int q = 0; q < mp.n; ++q)
-        if (mp.level[q] == cr.level) { mp.cq = q; mp.rowmap = cr.row_of_cell; mp.cells = B << (2 * (nbits - cr.level)); }
+        if (mp.level[q] == rows_level) { mp.cq = q; mp.rowmap = row_of_cell; mp.cells = B << (2 * (nbits - rows_level)); }
+    return mp.cq >= 0;
 }
 template <int VEC>
 __global__ __launch_bounds__(kThreads) void segsum_bwd_multi_kernel(MultiPlanes mp, const int32_t *__restrict__ cell,
@@ -505,7 +507,7 @@ __global__ __launch_bounds__(kThreads) void plane_sumpool2x2_kernel(const float 
     const int rf = 2 * rc;
     const int64_t fc = (b * rf + 2 * y) * rf + 2 * x;
     float4 a, bq, cq, d;
-    if (rowmap) {                         // compact fine rows (t2h_compact_next): an empty child has no row and contributes 0
+    if (rowmap) {                         // compact fine rows (T2H_COMPACT_SUMS): an empty child has no row and contributes 0
         const float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
         const int r0 = rowmap[fc], r1 = rowmap[fc + 1], r2 = rowmap[fc + rf], r3 = rowmap[fc + rf + 1];
         a = z; bq = z; cq = z; d = z;
@@ -809,7 +811,7 @@ __global__ __launch_bounds__(256, 2) void sample_relu_cellsums_v2_kernel(const f
             const float4 sum = make_float4(sum01.x, sum01.y, sum23.x, sum23.y);
             const uint32_t cm = (uint32_t)(cb + c);                      // child's Morton code inside the cell
             const int fx = (cx << d) + (int)compact1by1(cm), fy = (cy << d) + (int)compact1by1(cm >> 1);
-            // rowmap (t2h_compact_next): `sums` holds one row per occupied child; an empty child has none and writes nothing.
+            // rowmap (T2H_COMPACT_SUMS): `sums` holds one row per occupied child; an empty child has none and writes nothing.
             // s, e and the row are wave-uniform: a scalar branch
             int srow = (b * rs + fy) * rs + fx;
             if (rowmap) srow = e > s ? __builtin_amdgcn_readfirstlane(rowmap[srow]) : -1;
@@ -1169,7 +1171,7 @@ __global__ __launch_bounds__(kThreads) void segmean_finalize_kernel(const float 
     float den = (float)(cnt > 0 ? cnt : 1);
     int cx = (int)compact1by1(mk), cy = (int)compact1by1(mk >> 1), r = 1 << rbits;
     int64_t orow_i = ((int64_t)b * r + cy) * r + cx;
-    if (rowmap) {                         // compact rows (t2h_compact_next): an empty cell has no row and writes nothing
+    if (rowmap) {                         // compact rows (T2H_COMPACT_SUMS): an empty cell has no row and writes nothing
         if (cnt <= 0) return;
         orow_i = rowmap[orow_i];
     }
@@ -1944,10 +1946,8 @@ T2H_API int t2h_pool_rows_bwd(const float *gpooled, int ldg, const uint8_t *winn
 
 static int segreduce_fwd(bool mean, const float *feat, const int32_t *off0, int B, int N, int nbits, int level, int C,
                          float *plane_nhwc, int ld_out, void *workspace, size_t workspace_bytes, t2h_stream_t stream,
-                         const CompactRows &cr = CompactRows{}) {
+                         const int32_t *rowmap = nullptr) {
     if (!feat || !off0 || !plane_nhwc) return fail(T2H_ERR_ARG, "segmean_fwd: null pointer");
-    if (cr.row_of_cell && cr.level != level) return fail(T2H_ERR_ARG, "segsum_fwd: compact rows of level %d asked for level %d", cr.level, level);
-    const int32_t *rowmap = cr.row_of_cell;
     if (ld_out < C || (C % 4 == 0 && ld_out % 4 != 0)) return fail(T2H_ERR_ARG, "segmean_fwd: plane row stride %d < C = %d", ld_out, C);
     int rc = check_level("segmean_fwd", B, nbits, level, C);
     if (rc) return rc;
@@ -1993,14 +1993,13 @@ T2H_API int t2h_segmean_fwd(const float *feat, const int32_t *off0, int B, int N
 }
 
 T2H_API int t2h_segsum_fwd(const float *feat, const int32_t *off0, int B, int N, int nbits, int level, int C,
-                           float *plane_nhwc, int ld_plane, void *workspace, size_t workspace_bytes, t2h_stream_t stream) {
-    const CompactRows cr = take_compact();
-    return segreduce_fwd(false, feat, off0, B, N, nbits, level, C, plane_nhwc, ld_plane, workspace, workspace_bytes, stream, cr);
+                           float *plane_nhwc, int ld_plane, void *workspace, size_t workspace_bytes, t2h_stream_t stream,
+                           const int32_t *row_of_cell) {
+    return segreduce_fwd(false, feat, off0, B, N, nbits, level, C, plane_nhwc, ld_plane, workspace, workspace_bytes, stream, row_of_cell);
 }
 
 T2H_API int t2h_plane_sumpool2x2(const float *fine_nhwc, int ld_fine, int B, int r_fine, int C, float *coarse_nhwc, int ld_coarse,
-                                 t2h_stream_t stream) {
-    const CompactRows cr = take_compact();      // (the FINE side's rows; the level is the caller's to match: r_fine says nothing of it)
+                                 t2h_stream_t stream, const int32_t *fine_row_of_cell) {
     if (!fine_nhwc || !coarse_nhwc) return fail(T2H_ERR_ARG, "plane_sumpool2x2: null pointer");
     if (B < 1 || r_fine < 2 || (r_fine & 1) || C < 4 || C % 4 != 0 || ((uintptr_t)fine_nhwc & 15) || ((uintptr_t)coarse_nhwc & 15) ||
         ld_fine < C || ld_coarse < C || ld_fine % 4 != 0 || ld_coarse % 4 != 0)
@@ -2009,14 +2008,13 @@ T2H_API int t2h_plane_sumpool2x2(const float *fine_nhwc, int ld_fine, int B, int
     const int64_t total4 = (int64_t)B * rc * rc * (C / 4);
     hipLaunchKernelGGL(plane_sumpool2x2_kernel, dim3((unsigned)((total4 + kThreads - 1) / kThreads)), dim3(kThreads), 0,
                        as_stream(stream), fine_nhwc, total4, rc, C / 4, ld_fine, ld_coarse, coarse_nhwc,
-                       cr.row_of_cell);
+                       fine_row_of_cell);
     return check_launch("plane_sumpool2x2");
 }
 
 T2H_API int t2h_segsum_bwd_multi(const float *const *gplanes_nhwc, const int *levels, const int *lds, int n_planes,
                                  const int32_t *cell, int B, int N, int nbits, int C, const float *mask, const float *addend,
-                                 float *gfeat, t2h_stream_t stream) {
-    const CompactRows cr = take_compact();
+                                 float *gfeat, t2h_stream_t stream, const int32_t *row_of_cell, int rows_level) {
     if (!gplanes_nhwc || !levels || !lds || !cell || !gfeat) return fail(T2H_ERR_ARG, "segsum_bwd_multi: null pointer");
     if (n_planes < 1 || n_planes > kMaxMultiPlanes)
         return fail(T2H_ERR_ARG, "segsum_bwd_multi: 1..%d planes, got %d", kMaxMultiPlanes, n_planes);
@@ -2031,7 +2029,8 @@ T2H_API int t2h_segsum_bwd_multi(const float *const *gplanes_nhwc, const int *le
     }
     if (C % 4 == 0 && ((mask && ((uintptr_t)mask & 15)) || (addend && ((uintptr_t)addend & 15)) || ((uintptr_t)gfeat & 15)))
         return fail(T2H_ERR_ARG, "segsum_bwd_multi: rows must be 16-byte aligned");
-    set_compact(mp, cr, B, nbits);
+    if (!set_compact(mp, row_of_cell, rows_level, B, nbits))
+        return fail(T2H_ERR_ARG, "segsum_bwd_multi: compact rows of level %d, which no plane has", rows_level);
     const int64_t npts = rows_of(B, N);
     if (npts == 0) return T2H_OK;
     T2H_DISPATCH_VEC(C,
@@ -2115,18 +2114,14 @@ T2H_API int t2h_sample_relu_cellsums2(const float *plane_nhwc, const float *pts,
                                       int nbits, int level, int sum_level, int C, float *sums_nhwc, int ld_sums,
                                       float *pooled_nhwc, int ld_pooled, void *sign_bits, t2h_stream_t stream) {
     return t2h_sample_relu_cellsums_ordered(plane_nhwc, pts, dim, off0, B, N, nbits, level, sum_level, C, sums_nhwc, ld_sums,
-                                            pooled_nhwc, ld_pooled, sign_bits, nullptr, stream);
+                                            pooled_nhwc, ld_pooled, sign_bits, nullptr, stream, nullptr);
 }
 
 T2H_API int t2h_sample_relu_cellsums_ordered(const float *plane_nhwc, const float *pts, int dim, const int32_t *off0, int B, int N,
                                              int nbits, int level, int sum_level, int C, float *sums_nhwc, int ld_sums,
                                              float *pooled_nhwc, int ld_pooled, void *sign_bits, const int32_t *cell_order,
-                                             t2h_stream_t stream) {
-    const CompactRows cr = take_compact();
+                                             t2h_stream_t stream, const int32_t *row_of_cell) {
     if (!plane_nhwc || !pts || !off0 || !sums_nhwc) return fail(T2H_ERR_ARG, "sample_relu_cellsums: null pointer");
-    if (cr.row_of_cell && cr.level != sum_level)
-        return fail(T2H_ERR_ARG, "sample_relu_cellsums: compact rows of level %d asked for the sums of level %d", cr.level, sum_level);
-    const int32_t *rowmap = cr.row_of_cell;
     if (pooled_nhwc && (sum_level >= level || ld_pooled < C || ld_pooled % 4 != 0 || ((uintptr_t)pooled_nhwc & 15)))
         return fail(T2H_ERR_ARG, "sample_relu_cellsums: the pooled sums need sum_level < level and 16-byte aligned rows of >= C floats");
     int rc = check_level("sample_relu_cellsums", B, nbits, level, C);
@@ -2153,7 +2148,7 @@ T2H_API int t2h_sample_relu_cellsums_ordered(const float *plane_nhwc, const floa
     if (k0) while (nchild / (4 * gz * 2) >= quad && cells * chunks * gz < kMinWgs) gz *= 2;
     const dim3 grid((unsigned)((k0 ? cells : (cells >> 2)) * chunks * gz));               // K = 1: a 2 x 2 block of cells per workgroup
 #define T2H_V2_LAUNCH(KK, PP) hipLaunchKernelGGL((sample_relu_cellsums_v2_kernel<KK, PP>), grid, dim3(256), 0, as_stream(stream), \
-        plane_nhwc, pts, dim, off0, nbits, level, sum_level, C, sums_nhwc, ld_sums, bw, npts_m1, pooled_nhwc, ld_pooled, k0 ? order_k0 : order_k1, gz, rowmap)
+        plane_nhwc, pts, dim, off0, nbits, level, sum_level, C, sums_nhwc, ld_sums, bw, npts_m1, pooled_nhwc, ld_pooled, k0 ? order_k0 : order_k1, gz, row_of_cell)
     if (k0) { if (pooled_nhwc) T2H_V2_LAUNCH(0, true); else T2H_V2_LAUNCH(0, false); }
     else { if (pooled_nhwc) T2H_V2_LAUNCH(1, true); else T2H_V2_LAUNCH(1, false); }
 #undef T2H_V2_LAUNCH
@@ -2165,15 +2160,14 @@ T2H_API int t2h_sample_bwd_from_sums(const float *const *gplanes_nhwc, const int
                                      int level, int C, float *gplane_nhwc, void *workspace, size_t workspace_bytes,
                                      t2h_stream_t stream) {
     return t2h_sample_bwd_from_sums_ordered(gplanes_nhwc, levels, lds, n_planes, cell, mask, mask_is_bits, pts, dim, off0, B, N, nbits,
-                                            level, C, gplane_nhwc, workspace, workspace_bytes, nullptr, stream);
+                                            level, C, gplane_nhwc, workspace, workspace_bytes, nullptr, stream, nullptr, -1);
 }
 
 T2H_API int t2h_sample_bwd_from_sums_ordered(const float *const *gplanes_nhwc, const int *levels, const int *lds, int n_planes,
                                              const int32_t *cell, const void *mask, int mask_is_bits, const float *pts, int dim,
                                              const int32_t *off0, int B, int N, int nbits, int level, int C, float *gplane_nhwc,
                                              void *workspace, size_t workspace_bytes, const int32_t *cell_order,
-                                             t2h_stream_t stream) {
-    const CompactRows cr = take_compact();
+                                             t2h_stream_t stream, const int32_t *row_of_cell, int rows_level) {
     if (!gplanes_nhwc || !levels || !lds || !cell || !mask || !pts || !off0 || !gplane_nhwc)
         return fail(T2H_ERR_ARG, "sample_bwd_from_sums: null pointer");
     if (n_planes < 1 || n_planes > kMaxMultiPlanes)
@@ -2198,7 +2192,8 @@ T2H_API int t2h_sample_bwd_from_sums_ordered(const float *const *gplanes_nhwc, c
             return fail(T2H_ERR_ARG, "sample_bwd_from_sums: bad plane %d", q);
         mp.g[q] = gplanes_nhwc[q]; mp.level[q] = levels[q]; mp.ld[q] = lds[q];
     }
-    set_compact(mp, cr, B, nbits);
+    if (!set_compact(mp, row_of_cell, rows_level, B, nbits))
+        return fail(T2H_ERR_ARG, "sample_bwd_from_sums: compact rows of level %d, which no plane has", rows_level);
     int64_t groups = (int64_t)B << (2 * (nbits - level));
     float *partial = static_cast<float *>(workspace);
     int G = 1 << cp.lgG, P = kCellThreads >> cp.lgG;

@@ -22,15 +22,6 @@ int check_launch(const char *what);
 void note_kernel(const char *name);
 const char *noted_kernel();
 
-// Compact rows of one resolution's per-cell matrices (t2h_compact_next, include/t2h.h): what the caller asked for the NEXT launch
-// of this thread.  take_compact() hands it out once and clears it, so it can never reach a later call.
-struct CompactRows {
-    const int32_t *row_of_cell = nullptr;   // [B r r] plane order -> row of the compact matrix, -1 for an empty cell
-    int level = -1;                         // ALTO level of the compacted resolution
-    const int32_t *n_rows = nullptr;        // device int: rows in use
-};
-CompactRows take_compact();
-
 inline hipStream_t as_stream(t2h_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
 
 // (B, N) of the point-side entry points: B tiles of N rows each -- or, N < 0, a RAGGED batch of B tiles with -N rows in all

@@ -25,12 +25,6 @@ int fail(int code, const char *fmt, ...) {
 static thread_local const char *g_noted_kernel = "";
 void note_kernel(const char *name) { g_noted_kernel = name; }
 const char *noted_kernel() { return g_noted_kernel; }
-static thread_local CompactRows g_compact;
-CompactRows take_compact() {
-    const CompactRows c = g_compact;
-    g_compact = CompactRows{};
-    return c;
-}
 int check_launch(const char *what) {
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(T2H_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
@@ -228,9 +222,6 @@ T2H_API int t2h_abi_version(void) { return T2H_ABI_VERSION; }
 T2H_API const char *t2h_last_error_string(void) { return err_buf(); }
 T2H_API const char *t2h_last_kernel_name(void) { return noted_kernel(); }
 T2H_API void t2h_clear_kernel_name(void) { note_kernel(""); }
-T2H_API void t2h_compact_next(const int32_t *row_of_cell, int level, const int32_t *n_rows) {
-    g_compact.row_of_cell = row_of_cell; g_compact.level = level; g_compact.n_rows = n_rows;
-}
 
 T2H_API int t2h_debug_poison_lds(t2h_stream_t stream) {
     static unsigned *sink = nullptr;

@@ -54,10 +54,9 @@ def _segsum_into(tile, rows, level, dst, state=None):
     r = tile.R >> level
     ws_bytes = _lib.ws_bytes("t2h_segmean_workspace_bytes", tile.B, tile.N, tile.nbits, level, c)
     ws = _lib.workspace(ws_bytes, rows.device)
-    if state is not None:
-        state.request(level)
     _lib.call("t2h_segsum_fwd", _lib.ptr(rows), _lib.ptr(tile.off0), tile.B, tile.N, tile.nbits, level, c, dst.data_ptr(),
-              dst.stride(0), _lib.ptr(ws), ws_bytes, _lib.stream(), nbytes=4 * c * n + 4 * n + 4 * c * tile.B * r * r,
+              dst.stride(0), _lib.ptr(ws), ws_bytes, _lib.stream(), None if state is None else state.row_map(level),
+              nbytes=4 * c * n + 4 * n + 4 * c * tile.B * r * r,
               tag=_lib.timing() and f"t2h_segsum_fwd[C={c},r={r}]")
 
 
@@ -66,10 +65,9 @@ def _sumpool_into(tile, fine, level_fine, coarse, state=None):
     children."""
     c = fine.shape[1]
     r = tile.R >> level_fine
-    if state is not None:
-        state.request(level_fine)
     _lib.call("t2h_plane_sumpool2x2", fine.data_ptr(), fine.stride(0), tile.B, r, c, coarse.data_ptr(), coarse.stride(0),
-              _lib.stream(), nbytes=5 * c * tile.B * r * r, tag=_lib.timing() and f"t2h_plane_sumpool2x2[C={c}]")
+              _lib.stream(), None if state is None else state.row_map(level_fine), nbytes=5 * c * tile.B * r * r,
+              tag=_lib.timing() and f"t2h_plane_sumpool2x2[C={c}]")
 
 
 def _plane_args(planes):
@@ -84,17 +82,16 @@ def _gather(tile, planes, c, mask=None, state=None):
     """d rows [N, C] = (mask > 0 ?) sum over ``planes`` [(column block, level)] of block[cell_level(n)]: the adjoint of the sums."""
     out = torch.empty(tile.n_points, c, dtype=torch.float32, device=tile.device)
     arr, lvs, lds = _plane_args(planes)
-    if state is not None:
-        state.request_any(lv for _, lv in planes)
     _lib.call("t2h_segsum_bwd_multi", arr, lvs, lds, len(planes), _lib.ptr(tile.cell), tile.B, tile.N, tile.nbits, c,
               None if mask is None else _lib.ptr(mask), None, _lib.ptr(out), _lib.stream(),
+              *((None, -1) if state is None else state.rows_among(lv for _, lv in planes)),
               nbytes=4 * c * tile.n_points * (2 if mask is not None else 1) + 4 * tile.n_points
               + sum(4 * c * p.shape[0] for p, _ in planes), tag=_lib.timing() and f"t2h_segsum_bwd_multi[C={c},n={len(planes)}]")
     return out
 
 
 def cell_rows(tile, level):
-    """The occupied-row list of ALTO level ``level`` (include/t2h.h, ``t2h_compact_next``): one int32 buffer ``row_of_cell [P] |
+    """The occupied-row list of ALTO level ``level`` (include/t2h.h, compact per-cell matrices): one int32 buffer ``row_of_cell [P] |
     cell_of_row [P] | n_rows | ...`` with P = B r r, built on first use by the same entry point as the counts and kept for the
     tile's lifetime with the event behind its fill.  ``n_rows`` stays on the device: nothing here reads it."""
     cache = tile.__dict__.setdefault("_cell_rows", {})
@@ -104,8 +101,8 @@ def cell_rows(tile, level):
         p = tile.B * r * r
         buf = torch.empty(2 * p + 4 + (p + 2047) // 2048, dtype=torch.int32, device=tile.device)
         cnt = torch.empty(p, dtype=torch.float32, device=tile.device)
-        _lib.compact_next(buf.data_ptr(), level, buf.data_ptr() + 8 * p)
-        _lib.call("t2h_cell_counts", _lib.ptr(tile.off0), tile.B, tile.nbits, level, _lib.ptr(cnt), _lib.stream(), nbytes=28 * p)
+        _lib.call("t2h_cell_counts", _lib.ptr(tile.off0), tile.B, tile.nbits, level, _lib.ptr(cnt), _lib.stream(), buf.data_ptr(),
+                  nbytes=28 * p)
         tile.__dict__.setdefault("_cell_counts", {}).setdefault(level, cnt)      # the counts came out of the same launch: counts() finds them
         ready = _lib.Ready()
         ready.mark()
@@ -120,7 +117,7 @@ def counts(tile, level):
     if level not in cache:
         r = tile.R >> level
         cnt = torch.empty(tile.B * r * r, dtype=torch.float32, device=tile.device)
-        _lib.call("t2h_cell_counts", _lib.ptr(tile.off0), tile.B, tile.nbits, level, _lib.ptr(cnt), _lib.stream(),
+        _lib.call("t2h_cell_counts", _lib.ptr(tile.off0), tile.B, tile.nbits, level, _lib.ptr(cnt), _lib.stream(), None,
                   nbytes=12 * cnt.numel())
         cache[level] = cnt
     return cache[level]
@@ -218,12 +215,11 @@ class _DeferredLevel(torch.autograd.Function):
             if len(levels) > 1 and levels[1] == levels[0] + 1 and levels[0] < tile.level(r):
                 second = state.sums(idx + 1, levels[1])
             order = tile.cell_order(tile.level(r))
-            state.request(levels[0])
             _lib.call("t2h_sample_relu_cellsums_ordered", _lib.ptr(q_rows), _lib.ptr(tile.pts), tile.dim, _lib.ptr(tile.off0), tile.B,
                       tile.N, tile.nbits, tile.level(r), levels[0], c2, finest.data_ptr(), finest.stride(0),
                       None if second is None else second.data_ptr(), 0 if second is None else second.stride(0),
                       None if bits is None else _lib.ptr(bits), None if order is None else _lib.ptr(order), _lib.stream(),
-                      nbytes=4 * q_rows.numel() + 12 * tile.n_points + 4 * c2 * finest.shape[0]
+                      state.row_map(levels[0]), nbytes=4 * q_rows.numel() + 12 * tile.n_points + 4 * c2 * finest.shape[0]
                       + (0 if bits is None else (c2 // 8) * tile.n_points) + (0 if second is None else 4 * c2 * second.shape[0]),
                       tag=_lib.timing() and f"t2h_sample_relu_cellsums[C={c2},r={r}]")
             state.pool_down(idx + 1, start=1 if second is not None else 0)
@@ -246,9 +242,8 @@ class _DeferredLevel(torch.autograd.Function):
         mlp.linear_dgrad_(x, a_all, acc, bx3=True, row_limit=state.row_limit(lv))     # "dx = dy w" is exactly x @ A
         cnt = counts(tile, lv)
         out = torch.empty_like(acc)
-        state.request(lv)
         _lib.call("t2h_mean_bias_fwd", _lib.ptr(acc), _lib.ptr(cnt), _lib.ptr(const), acc.shape[0], acc.shape[1], _lib.ptr(out),
-                  _lib.stream(), nbytes=8 * acc.numel() + 4 * acc.shape[0])
+                  _lib.stream(), state.row_map(lv), nbytes=8 * acc.numel() + 4 * acc.shape[0])
         ctx.state, ctx.idx, ctx.r, ctx.has_base = state, idx, r, idx == 0
         ctx.const_shape = const.shape
         ctx.mask_is_bits = mask_is_bits
@@ -274,9 +269,8 @@ class _DeferredLevel(torch.autograd.Function):
         dconst = torch.empty(ctx.const_shape, dtype=torch.float32, device=g.device) if (ctx.needs_input_grad[2] or cached) else None
         ws_bytes = _lib.ws_bytes("t2h_mean_bias_bwd_workspace_bytes", p, c)
         ws = _lib.workspace(ws_bytes, g.device)
-        state.request(lv)
         _lib.call("t2h_mean_bias_bwd", _lib.ptr(g), _lib.ptr(cnt), p, c, _lib.ptr(dacc), None if dconst is None else _lib.ptr(dconst),
-                  _lib.ptr(ws), ws_bytes, _lib.stream(), nbytes=8 * p * c + 4 * p)
+                  _lib.ptr(ws), ws_bytes, _lib.stream(), state.row_map(lv), nbytes=8 * p * c + 4 * p)
         x = state.S[lv][:, :k]
         da = ga_thru
         if cached:
@@ -437,15 +431,15 @@ class Deferred:
         self.a_all, self.const = None, None
         self.n_done = 0
 
-    def request(self, lv):
-        """Before a launch that touches the sum / gradient matrix of ALTO level ``lv``: ask for addressing by occupied row where
-        that level is the compact one (``t2h_compact_next``; the launch takes the request)."""
-        if lv == self.compact_lv:
-            _lib.compact_next(self._row_ptr, lv, self._n_rows_ptr)
+    def row_map(self, lv):
+        """Device pointer to ``row_of_cell`` of level ``lv``'s sum / gradient matrix where that level is the compact one (its rows are
+        addressed by occupied row), None where it holds one row per cell."""
+        return self._row_ptr if lv == self.compact_lv else None
 
-    def request_any(self, levels):
-        if self.compact_lv is not None and self.compact_lv in levels:
-            self.request(self.compact_lv)
+    def rows_among(self, levels):
+        """(row_of_cell, rows_level) for a launch that reads the matrices of several ``levels``: the compact one's where it is among
+        them, else (None, -1)."""
+        return (self._row_ptr, self.compact_lv) if self.compact_lv in levels else (None, -1)
 
     def row_limit(self, lv):
         """Device pointer to the number of rows in use of level ``lv``'s matrices, None where they hold one row per cell."""
@@ -504,10 +498,10 @@ class Deferred:
             ws = _lib.workspace(ws_bytes, h.device)
             dq = torch.empty(tile.B * r * r, c2, dtype=torch.float32, device=h.device)
             order = tile.cell_order(level) if mask_is_bits else None
-            self.request_any([lv for _, lv in planes])
             _lib.call("t2h_sample_bwd_from_sums_ordered", arr, lvs, lds, len(planes), _lib.ptr(tile.cell), _lib.ptr(h),
                       1 if mask_is_bits else 0, _lib.ptr(tile.pts), tile.dim, _lib.ptr(tile.off0), tile.B, tile.N, tile.nbits,
                       level, c2, _lib.ptr(dq), _lib.ptr(ws), ws_bytes, None if order is None else _lib.ptr(order), _lib.stream(),
+                      *self.rows_among([lv for _, lv in planes]),
                       nbytes=(c2 // 8 if mask_is_bits else 4 * c2) * tile.n_points + 12 * tile.n_points + 4 * dq.numel()
                       + sum(4 * c2 * p.shape[0] for p, _ in planes), tag=_lib.timing() and f"t2h_sample_bwd_from_sums[C={c2},r={r}]")
             return dq

@@ -544,7 +544,7 @@ class _Conv1x1(torch.autograd.Function):
         nws = _lib.ws_bytes("t2h_linear_wgrad_workspace_bytes", m, cin, cout)
         ws = _lib.workspace(nws, g.device)
         _lib.call("t2h_linear_wgrad", _lib.ptr(g), ldg, _lib.ptr(x), cin, m, cin, cout, _lib.ACCUM if direct else 0,
-                  _lib.ptr(dw), _lib.ptr(db) if db is not None else None, _lib.ptr(ws), nws, _lib.stream(),
+                  _lib.ptr(dw), _lib.ptr(db) if db is not None else None, _lib.ptr(ws), nws, _lib.stream(), None,
                   nbytes=4 * (m * cin + m * cout + cin * cout), flops=2 * m * cin * cout,
                   tag=_lib.timing() and f"t2h_linear_wgrad[N={cout},K={cin}]")
         ga = g if ctx.has_addend else None

@@ -93,11 +93,9 @@ def _gemm_bx3(x, w, w_is_kn, bias, mask, y, relu_out, accumulate, tag, row_limit
     nws = _lib.ws_bytes("t2h_gemm_bx3_workspace_bytes", m, k, n)
     ws = _lib.workspace(nws, x.device)
     flags = (_lib.RELU_OUT if relu_out else 0) | (_lib.ACCUM if accumulate else 0) | (_lib.F16X2 if grid._h2() else 0)
-    wf = _lib.ptr(grid.split_weights.get_gemm(w, w_is_kn))               # (may launch the split: before the request below)
-    if row_limit is not None:
-        _lib.compact_next(None, -1, row_limit)
+    wf = _lib.ptr(grid.split_weights.get_gemm(w, w_is_kn))
     _lib.call("t2h_gemm_bx3", xp, ldx, wf, bias.data_ptr() if bias is not None else None,
-              mp, ldm, yp, ldy, m, k, n, flags, _lib.ptr(ws), nws, _lib.stream(),
+              mp, ldm, yp, ldy, m, k, n, flags, _lib.ptr(ws), nws, _lib.stream(), row_limit,
               nbytes=4 * (m * k + m * n + n * k + (m * n if mask is not None else 0)), flops=2 * m * k * n, tag=_lib.timing() and tag)
     return y
 
@@ -172,9 +170,8 @@ def linear_wgrad_(dy, x, dw, db, relu_in=False, accumulate=False, defer=False, r
     if bx3:
         _lib.call("t2h_gemm_bx3_wgrad", gp, ldg, xp, ldx, m, k, n, *outs, flags, ws.data_ptr(), ws_bytes, _lib.stream(), **cost)
     else:
-        if row_limit is not None:
-            _lib.compact_next(None, -1, row_limit)
-        _lib.call("t2h_linear_wgrad", gp, ldg, xp, ldx, m, k, n, flags, *outs, ws.data_ptr(), ws_bytes, _lib.stream(), **cost)
+        _lib.call("t2h_linear_wgrad", gp, ldg, xp, ldx, m, k, n, flags, *outs, ws.data_ptr(), ws_bytes, _lib.stream(), row_limit,
+                  **cost)
 
 
 # ------------------------------------------------------------------------------------------------ backward-pass state
