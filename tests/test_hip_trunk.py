@@ -225,28 +225,9 @@ def test_fused_backward_vs_float64_with_the_same_masks(name):
     got = mlp._trunk_backward_fused(tile, tile.pts, params, nets, pooled_f, hrs, winners, g_out)
     assert all(g is not None for g in got)
 
+    import trunk_ref
     d = torch.float64
-    w = [p.to(d) for p in params]
-    want = [None] * len(params)
-    go = g_out.to(d)
-    out_last = nets[-1].to(d)
-    want[-2], want[-1] = go.t() @ torch.relu(out_last), go.sum(0)
-    g = (go @ w[-2]) * (out_last > 0)
-    cell = tile.cell.long()
-    uniq, inv = torch.unique_consecutive(cell, return_inverse=True)
-    for i in range(nb - 1, -1, -1):
-        w0, b0, w1, b1, ws = w[2 + 5 * i: 7 + 5 * i]
-        x, hr = cats[i].to(d), hrs[i].to(d)
-        dhr = (g @ w1) * (hr > 0)
-        want[2 + 5 * i: 7 + 5 * i] = [dhr.t() @ torch.relu(x), dhr.sum(0), g.t() @ hr, g.sum(0), g.t() @ x]
-        dx = g @ ws + (dhr @ w0) * (x > 0)
-        if i > 0:
-            sums = torch.zeros(len(uniq), 32, dtype=d, device=dx.device).index_add_(0, inv, dx[:, 32:])
-            bits = winners[i - 1]
-            mask = torch.stack([(bits[:, ch // 4] >> (ch % 4)) & 1 for ch in range(32)], 1).to(d)
-            g = dx[:, :32] + mask * sums[inv]
-        else:
-            want[0], want[1] = dx.t() @ tile.pts.to(d), dx.sum(0)
+    want = trunk_ref.fused_backward_float64(tile, params, nets, hrs, winners, cats, g_out)
     for k, (a, b) in enumerate(zip(got, want)):
         scale = b.abs().max().item() + 1e-30
         assert (a.to(d) - b).abs().max().item() <= 1e-5 * scale, f"param {k}: {(a.to(d) - b).abs().max().item() / scale:.2e}"
