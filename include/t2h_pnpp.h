@@ -1,8 +1,9 @@
 /* t2h_pnpp.h -- C ABI of the PointNet++ point stages in libt2h_hip.so (csrc/pnpp.hip): farthest point sampling, radius
  * grouping, grouped rows, grouped max and 3-nearest-neighbour feature propagation -- the index and gather work of the
  * reference's tomosar2height/encoder/pointnetpp.py (farthest_point_sample :220-241, query_ball_point :244-264,
- * sample_and_group :279-296, torch.max(new_points, 2) :55, PointNetFeaturePropagation.forward :90-97).  Forward only: the
- * encoder built on them runs in eval().
+ * sample_and_group :279-296, torch.max(new_points, 2) :55, PointNetFeaturePropagation.forward :90-97), and the adjoints of the
+ * grouped rows, the grouped max and the propagation with respect to the FEATURES (xyz is input data: sampling, grouping, the
+ * 3-NN indices and weights have no gradient).  The encoder built on them runs in eval().
  *
  * Same conventions as t2h.h: device pointers owned by the caller, no allocation, no state, stream-ordered calls, 0 or a
  * negative T2H_ERR_* code, every argument validated before any launch.  The entries live in the same library but are typed by
@@ -11,7 +12,9 @@
  * Inputs are dense [B, N, ...] fp32.  Every squared distance is taken by differences,
  *   d2 = ((dx * dx + dy * dy) + dz * dz),  dx = x - cx, ...   each operation rounded once in fp32, no fused multiply-add,
  * never by the reference's -2 x.y + |x|^2 + |y|^2 matmul form, whose rounding depends on the BLAS underneath.  No kernel
- * uses a float atomic, waits for another workgroup or depends on scheduling: two runs give the same bytes.
+ * uses a float atomic, waits for another workgroup or depends on scheduling: two runs give the same bytes.  (t2h_index_transpose
+ * places entries with INTEGER atomics and then orders every segment, so its result does not depend on scheduling either.)
+ * No entry needs a workspace but t2h_fps: every other buffer, scratch included, is a typed argument whose size is stated here.
  */
 #ifndef T2H_PNPP_H_
 #define T2H_PNPP_H_
@@ -63,6 +66,49 @@ int t2h_group_max(const float *rows, int ld, int64_t groups, int nsample, int C,
  * `repeat` branch: idx 0, weight (1, 0, 0), out = the one source row (any D >= 1).  S == 2 is refused, as the reference fails on it. */
 int t2h_three_nn_interp(const float *xyz1, const float *xyz2, const float *points2, int B, int N, int S, int D, int64_t *idx,
                         float *weight, float *out, t2h_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------------------------- adjoints */
+#define T2H_TRANSPOSE_SORT_MAX 8192 /* longest segment t2h_index_transpose orders in LDS (4 bytes per entry); longer: see there */
+#define T2H_GATHER_CHUNK 64         /* entries per chunk of t2h_rows_gather_bwd's sums */
+#define T2H_GATHER_LANES 4          /* interleaved chunk sums per output element */
+
+/* Adjoint of t2h_group_max (same rows, ld, groups, nsample, C; out = its result [groups, C]; gout [groups, C] = the gradient of
+ * out): grows [groups * nsample, gld], gld >= C.  Per group and column c < C the LOWEST row j of the group with
+ * rows[j, c] - out[c] == 0 (fp32 subtraction; a NaN or infinite maximum matches no row) receives gout[c]; every other row of the
+ * column receives +0; columns C .. gld are +0.  relu != 0: a column with NOT (out[c] > 0) receives +0 in every row -- the mask of
+ * a ReLU applied to `rows` before the max, fused (max and ReLU commute).
+ * The tie rule cannot change a parameter gradient.  Rows of a group that tie are either padded slots -- the ball query repeats
+ * the first index, so they are copies of ONE source row with the same layer inputs, and the sum over the group of
+ * (row gradient x layer input) is the same whichever copy takes it, as is the sum the gather's adjoint forms for that source --
+ * or distinct rows that tie at 0, the only value ReLU makes common, where relu != 0 gives +0 to all of them. */
+int t2h_group_max_bwd(const float *rows, int ld, int64_t groups, int nsample, int C, const float *out, const float *gout, int relu,
+                      float *grows, int gld, t2h_stream_t stream);
+
+/* Transpose of an index list: the CSR of idx [B, E] int64 by VALUE over N sources.  offsets [B, N + 1] int32, entries [B, E]
+ * int32: entries[b, offsets[b, i] .. offsets[b, i + 1]) are the positions e with idx[b, e] == i in ASCENDING e -- per cloud,
+ * entries = the stable argsort of idx.  An index outside [0, N) counts as N - 1 (t2h_group_rows reads row N - 1 for the
+ * empty-group marker N).  cursor [B, N] int32 is scratch (any contents; overwritten).
+ * Four launches behind a memset: counts (integer atomic adds into cursor), an exclusive scan per cloud, placement (an integer
+ * atomic add hands each entry the next free slot of its segment, in an order that depends on scheduling), then one workgroup
+ * per segment orders it by e: up to T2H_TRANSPOSE_SORT_MAX entries by a min/max sorting network in LDS, a longer one by
+ * re-reading idx[b, :] in order.  The keys of a segment are distinct, so the bytes are fixed. */
+int t2h_index_transpose(const int64_t *idx, int B, int E, int N, int32_t *offsets, int32_t *entries, int32_t *cursor,
+                        t2h_stream_t stream);
+
+/* Adjoint of a row gather through (offsets, entries) of t2h_index_transpose: out [B, N, D],
+ *   out[b, i, d] = sum over e in entries[b, offsets[b, i] .. offsets[b, i + 1]) of w[b, e] * g[(b * E + e) / fan, col0 + d],
+ * g [B * E / fan, gld] fp32 with gld >= col0 + D, weight [B, E] fp32 or NULL (w = 1), fan = 1 or 3 (E % fan == 0).
+ *   fan = 1, col0 = 3, weight NULL: the adjoint of t2h_group_rows with respect to `points` (g = the gradient of rows, gld = ld);
+ *   fan = 3, weight = the 3-NN weights: the adjoint of t2h_three_nn_interp with respect to `points2` (g = the gradient of out).
+ * S == 1 (the `repeat` branch) is the same call with N = 1: every entry in segment 0, weights (1, 0, 0).
+ * Association, the same for every element: the segment is cut into chunks of T2H_GATHER_CHUNK consecutive entries, chunk k =
+ * entries offsets[b, i] + 64 k ..; a chunk sum starts from +0 and adds its terms in ascending order, term = w * g rounded, then
+ * added (two roundings, no fused multiply-add); an entry with w == 0 is skipped, it adds no term (not even 0 * g, which an
+ * infinite g would turn into NaN).  Lane sum y of T2H_GATHER_LANES starts from +0 and adds the chunk sums k = y, y + 4, y + 8,
+ * ... in ascending k; out = ((lane_0 + lane_1) + lane_2) + lane_3.  An empty segment gives +0.  One workgroup per (b, i) and
+ * 64 columns, one lane per column. */
+int t2h_rows_gather_bwd(const float *g, int gld, int col0, int D, const float *weight, int fan, const int32_t *offsets,
+                        const int32_t *entries, int B, int E, int N, float *out, t2h_stream_t stream);
 
 #ifdef __cplusplus
 }

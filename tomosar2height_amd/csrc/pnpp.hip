@@ -1,5 +1,6 @@
 // PointNet++ point stages on the device (reference: tomosar2height/encoder/pointnetpp.py; ABI in include/t2h_pnpp.h):
-// farthest point sampling, radius grouping, grouped rows, grouped max, 3-nearest-neighbour feature propagation.  Forward only.
+// farthest point sampling, radius grouping, grouped rows, grouped max, 3-nearest-neighbour feature propagation, and the adjoints
+// of the last three with respect to the features.
 //
 // FPS: the running distance of every point to the chosen set and, per centroid, an arg-max with the lowest index among equal
 //   maxima.  Distances are sums of squares, so never negative and never NaN after the min: their bit patterns order as unsigned
@@ -16,6 +17,11 @@
 // THREE-NN: one target per thread, sources staged through LDS 512 at a time, a sorted list of three (d2, index) in registers;
 //   a source replaces an entry only when strictly closer, and sources arrive in index order, so equal d2 keep the lower index.
 //
+// ADJOINTS (features only: xyz is data).  Grouped max: the gradient goes to the lowest row that holds the maximum.  A gather's
+//   adjoint is a sum per source over the positions that read it: t2h_index_transpose builds that list (a CSR by index value,
+//   each segment in ascending position) with integer atomics and a per-segment sort, and rows_gather_bwd_kernel walks it, one
+//   workgroup per source row, one lane per column, in the fixed association of include/t2h_pnpp.h.  No float atomic.
+//
 // Compare results and vector selects (audited on the emitted assembly with isa_pass.lifetimes, figures in
 //   DESIGN.md section 4.9).  These kernels run in the same forward as the split convolutions of the U-Net, on the same stream,
 //   and could share a CU with those of another stream.  fps_one, group_rows, nn_interp and nn_repeat contain no v_cndmask:
@@ -23,7 +29,8 @@
 //   v_min_u32, grids are per group so that no flat index is divided.  fps_slice and group_max keep one v_cndmask 0, 1 from a
 //   scalar-written mask; the ball query's ballot is read by v_mbcnt as data and its store re-compares in a branch.
 //   three_nn_kernel is NOT select-free: its sorted insertion is 20 v_cndmask, each fed by a compare at most 6 instructions
-//   earlier.
+//   earlier.  The adjoint kernels are written to the same rule: equality and the ReLU mask come from opaque v_min_u32 /
+//   v_med3_i32 and an AND, the sort exchanges by v_min_i32 / v_max_i32, guarded stores and the zero-weight skip are branches.
 #include <math.h>
 
 #include "t2h_common.h"
@@ -35,6 +42,11 @@ constexpr int kFpsOneThreads = 512;
 constexpr int kFpsSliceThreads = 256;
 constexpr int kNnThreads = 256;
 constexpr int kNnChunk = 512;
+constexpr int kSortMax = T2H_TRANSPOSE_SORT_MAX;
+constexpr int kGatherChunk = T2H_GATHER_CHUNK;
+constexpr int kGatherWaves = T2H_GATHER_LANES;
+static_assert(kGatherChunk == 64, "a chunk's entries are held one per lane of a wave");
+static_assert((kSortMax & (kSortMax - 1)) == 0, "the sorting network pads to a power of two");
 
 __device__ inline float pn_d2(float x, float y, float z, float cx, float cy, float cz) {
     const float dx = __fsub_rn(x, cx), dy = __fsub_rn(y, cy), dz = __fsub_rn(z, cz);
@@ -289,6 +301,217 @@ __global__ __launch_bounds__(256) void nn_repeat_kernel(const float *__restrict_
     }
 }
 
+// ---------------------------------------------------------------------------------------------------- adjoints
+// 0 where a == b, 1 elsewhere, and the ReLU mask, by opaque integer instructions (no compare, see the head of this file)
+__device__ inline unsigned pn_differs(unsigned a, unsigned b) {
+    unsigned d;
+    asm("v_min_u32 %0, %1, 1" : "=v"(d) : "v"(a ^ b));
+    return d;
+}
+// all ones where x > 0, 0 elsewhere (+-0, negative, NaN with the sign bit): -med3(bits, 0, 1) on the bits as a signed integer
+__device__ inline unsigned pn_positive_mask(float x) {
+    int m;
+    asm("v_med3_i32 %0, %1, 0, 1" : "=v"(m) : "v"(__float_as_int(x)));
+    return (unsigned)(-m);
+}
+
+// grid (groups), 256 threads over the columns 0 .. gld.  Pass 1 finds the lowest row j with rows[j, c] - out[c] == 0 as an
+// integer minimum of j | 0x7fffffff * (difference != 0); pass 2 writes gout & -(j == first) row by row.
+__global__ __launch_bounds__(256) void group_max_bwd_kernel(const float *__restrict__ rows, int ld, int nsample, int C,
+                                                            const float *__restrict__ out, const float *__restrict__ gout,
+                                                            int relu, float *__restrict__ grows, int gld) {
+    const size_t g = blockIdx.x;
+    const unsigned keep_all = relu ? 0u : 0xffffffffu;                    // (uniform)
+    for (int c = threadIdx.x; c < gld; c += 256) {
+        float *dst = grows + g * nsample * gld + c;
+        if (c >= C) {
+            for (int j = 0; j < nsample; ++j) dst[(size_t)j * gld] = 0.0f;
+            continue;
+        }
+        const float o = out[g * C + c];
+        const unsigned gv = __float_as_uint(gout[g * C + c]) & (pn_positive_mask(o) | keep_all);
+        const float *p = rows + g * nsample * ld + c;
+        unsigned first = 0x7fffffffu;
+        for (int j = 0; j < nsample; ++j) {
+            const unsigned differs = pn_differs(__float_as_uint(__fsub_rn(p[(size_t)j * ld], o)) & 0x7fffffffu, 0u);
+            first = min(first, (unsigned)j | ((0u - differs) >> 1));
+        }
+        for (int j = 0; j < nsample; ++j)
+            dst[(size_t)j * gld] = __uint_as_float(gv & (pn_differs((unsigned)j, first) - 1u));
+    }
+}
+
+__device__ inline int pn_clamp_index(long long v, int N) {
+    return (int)(v < 0 || v >= N ? N - 1 : v);
+}
+
+// grid (ceil(E / 256), B): cursor[b, i] += 1 per entry with index i (integer atomics: the counts do not depend on the order)
+__global__ __launch_bounds__(256) void transpose_count_kernel(const long long *__restrict__ idx, int E, int N,
+                                                              int *__restrict__ cursor) {
+    const int b = blockIdx.y, e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= E) return;
+    atomicAdd(cursor + (size_t)b * N + pn_clamp_index(idx[(size_t)b * E + e], N), 1);
+}
+
+// grid (B), 256 threads: offsets[b, 0 .. N] = exclusive prefix sums of the counts, 256 at a time behind a running total;
+// cursor[b, i] = offsets[b, i]
+__global__ __launch_bounds__(256) void transpose_scan_kernel(int N, int *__restrict__ offsets, int *__restrict__ cursor) {
+    __shared__ int part[256];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    int *cur = cursor + (size_t)b * N, *off = offsets + (size_t)b * (N + 1);
+    int run = 0;
+    for (int base = 0; base < N; base += 256) {
+        const int i = base + tid;
+        int count = 0;
+        if (i < N) count = cur[i];
+        part[tid] = count;
+        __syncthreads();
+        for (int o = 1; o < 256; o <<= 1) {                               // Hillis-Steele inclusive scan
+            int add = 0;
+            if (tid >= o) add = part[tid - o];
+            __syncthreads();
+            part[tid] += add;
+            __syncthreads();
+        }
+        const int incl = part[tid], total = part[255];
+        if (i < N) {
+            off[i] = run + incl - count;
+            cur[i] = run + incl - count;
+        }
+        run += total;
+        __syncthreads();
+    }
+    if (tid == 0) off[N] = run;
+}
+
+// grid (ceil(E / 256), B): entry e takes the next free slot of its segment (the order inside a segment depends on scheduling;
+// transpose_sort_kernel then orders it)
+__global__ __launch_bounds__(256) void transpose_place_kernel(const long long *__restrict__ idx, int E, int N,
+                                                              int *__restrict__ cursor, int *__restrict__ entries) {
+    const int b = blockIdx.y, e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= E) return;
+    const int pos = atomicAdd(cursor + (size_t)b * N + pn_clamp_index(idx[(size_t)b * E + e], N), 1);
+    if (pos >= 0 && pos < E) entries[(size_t)b * E + pos] = e;            // (always inside: the counts were taken from the same idx)
+}
+
+// grid (N, B), 256 threads: one segment per workgroup, ordered by e.  Up to kSortMax entries: in LDS, padded with INT_MAX to a
+// power of two, by a sorting network whose every exchange is (min, max) -- each merge opens with the mirrored partner
+// i ^ (k - 1), then halves the distance -- so no direction is ever selected.  Longer segments are written afresh: the workgroup
+// walks e = 0 .. E in index order, 256 at a time, and hands the matching entries consecutive slots (ballot + population of
+// the lower lanes, as the ball query).
+__global__ __launch_bounds__(256) void transpose_sort_kernel(const long long *__restrict__ idx, int E, int N,
+                                                             const int *__restrict__ offsets, int *__restrict__ entries) {
+    __shared__ int key[kSortMax];
+    __shared__ int wave_count[4];
+    const int b = blockIdx.y, i = blockIdx.x, tid = threadIdx.x;
+    const int *off = offsets + (size_t)b * (N + 1);
+    const int lo = max(0, min(off[i], E)), hi = max(lo, min(off[i + 1], E)), len = hi - lo;
+    if (len < 2) return;                                                  // (uniform)
+    int *seg = entries + (size_t)b * E + lo;
+    if (len <= kSortMax) {
+        int P = 2;
+        while (P < len) P <<= 1;
+        for (int t = tid; t < P; t += 256) {
+            int v = 0x7fffffff;
+            if (t < len) v = seg[t];
+            key[t] = v;
+        }
+        __syncthreads();
+        for (int lk = 1; (1 << lk) <= P; ++lk) {                          // merges of k = 2^lk keys
+            const int k = 1 << lk, half = k >> 1;
+            for (int t = tid; t < (P >> 1); t += 256) {
+                const int base = (t >> (lk - 1)) << lk, within = t & (half - 1);
+                const int a = base + within, c = base + (k - 1 - within);
+                const int x = key[a], y = key[c];
+                key[a] = min(x, y);
+                key[c] = max(x, y);
+            }
+            __syncthreads();
+            for (int lj = lk - 2; lj >= 0; --lj) {                        // distances j = 2^lj
+                const int j = 1 << lj;
+                for (int t = tid; t < (P >> 1); t += 256) {
+                    const int a = ((t >> lj) << (lj + 1)) + (t & (j - 1)), c = a + j;
+                    const int x = key[a], y = key[c];
+                    key[a] = min(x, y);
+                    key[c] = max(x, y);
+                }
+                __syncthreads();
+            }
+        }
+        for (int t = tid; t < len; t += 256) seg[t] = key[t];
+        return;
+    }
+    const long long *src = idx + (size_t)b * E;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);       // (scalar: the sums below select by it)
+    int run = 0;
+    for (int base = 0; base < E; base += 256) {
+        const int e = base + tid;
+        int id = -1;
+        if (e < E) id = pn_clamp_index(src[e], N);
+        const unsigned long long in = __ballot(id == i);
+        if (lane == 0) wave_count[wave] = __popcll(in);
+        __syncthreads();
+        int before = 0, total = 0;
+        for (int w = 0; w < 4; ++w) {                                     // (uniform per wave: scalar)
+            const int n = wave_count[w];
+            if (w < wave) before += n;
+            total += n;
+        }
+        const int pos = run + before + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(in >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)in, 0u));
+        if (id == i && pos < len) seg[pos] = e;                           // (compared again at the use: a branch)
+        run += total;
+        __syncthreads();
+    }
+}
+
+// grid (N, B, ceil(D / 64)), block (64, kGatherWaves): one destination row and 64 columns per workgroup, one lane per column.
+// Wave y sums the chunks k = y, y + kGatherWaves, ... of kGatherChunk consecutive entries of the segment, each chunk from +0 in
+// ascending order, the chunk sums in ascending k from +0; out = ((s_0 + s_1) + s_2) + s_3.  Separate multiply and add.
+__global__ __launch_bounds__(64 * kGatherWaves) void rows_gather_bwd_kernel(const float *__restrict__ g, int gld, int col0, int D,
+                                                                            const float *__restrict__ weight, int fan,
+                                                                            const int *__restrict__ offsets,
+                                                                            const int *__restrict__ entries, int E, int N,
+                                                                            float *__restrict__ out) {
+    __shared__ float lane_sum[kGatherWaves][64];
+    const int b = blockIdx.y, i = blockIdx.x, d = blockIdx.z * 64 + threadIdx.x, y = threadIdx.y;
+    const int dc = min(d, D - 1);
+    const int *off = offsets + (size_t)b * (N + 1);
+    const int lo = max(0, min(off[i], E)), hi = max(lo, min(off[i + 1], E));
+    const int *seg = entries + (size_t)b * E;
+    const float *w = weight ? weight + (size_t)b * E : nullptr;
+    const float *src = g + (size_t)b * (size_t)(E / fan) * gld + col0 + dc;
+    float s = 0.0f;
+    for (int c0 = lo + y * kGatherChunk; c0 < hi; c0 += kGatherWaves * kGatherChunk) {
+        const int n = min(kGatherChunk, hi - c0);
+        // the chunk's entries and weights, one per lane (lanes past the chunk repeat its last entry and are not read)
+        const int mine = max(0, min(seg[c0 + min((int)threadIdx.x, n - 1)], E - 1));
+        const int my_row = fan == 3 ? mine / 3 : mine;
+        float my_w = 1.0f;
+        if (w) my_w = w[mine];
+        float p = 0.0f;
+        for (int k = 0; k < n; k += 4) {                                  // four rows in flight; added in ascending order
+            float v[4], we[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int ku = min(k + u, n - 1);                         // (uniform)
+                v[u] = src[(size_t)__builtin_amdgcn_readlane(my_row, ku) * gld];
+                we[u] = __uint_as_float(__builtin_amdgcn_readlane(__float_as_uint(my_w), ku));
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u)                                   // (uniform conditions: branches; w == 0 adds nothing)
+                if (k + u < n && we[u] != 0.0f) p = __fadd_rn(p, __fmul_rn(we[u], v[u]));
+        }
+        s = __fadd_rn(s, p);
+    }
+    lane_sum[y][threadIdx.x] = s;
+    __syncthreads();
+    if (y == 0 && d < D) {
+        float t = lane_sum[0][threadIdx.x];
+        for (int k = 1; k < kGatherWaves; ++k) t = __fadd_rn(t, lane_sum[k][threadIdx.x]);
+        out[((size_t)b * N + i) * D + d] = t;
+    }
+}
+
 static unsigned blocks_for(long long total, int per) { return (unsigned)((total + per - 1) / per); }
 
 }  // namespace t2h
@@ -376,4 +599,42 @@ T2H_API int t2h_three_nn_interp(const float *xyz1, const float *xyz2, const floa
                        weight, N, S, D, out);
     note_kernel("three_nn_kernel");
     return check_launch("three_nn_interp");
+}
+
+T2H_API int t2h_group_max_bwd(const float *rows, int ld, int64_t groups, int nsample, int C, const float *out, const float *gout,
+                              int relu, float *grows, int gld, t2h_stream_t stream) {
+    if (!rows || !out || !gout || !grows) return fail(T2H_ERR_ARG, "group_max_bwd: null pointer");
+    if (groups < 1 || groups > 0x7fffffffll || nsample < 1 || C < 1 || ld < C || gld < C)
+        return fail(T2H_ERR_ARG, "group_max_bwd: bad shape groups=%lld nsample=%d C=%d ld=%d gld=%d", (long long)groups, nsample, C, ld, gld);
+    hipLaunchKernelGGL(group_max_bwd_kernel, dim3((unsigned)groups), dim3(256), 0, as_stream(stream), rows, ld, nsample, C, out, gout,
+                       relu ? 1 : 0, grows, gld);
+    note_kernel("group_max_bwd_kernel");
+    return check_launch("group_max_bwd");
+}
+
+T2H_API int t2h_index_transpose(const int64_t *idx, int B, int E, int N, int32_t *offsets, int32_t *entries, int32_t *cursor,
+                                t2h_stream_t stream) {
+    if (!idx || !offsets || !entries || !cursor) return fail(T2H_ERR_ARG, "index_transpose: null pointer");
+    if (B < 1 || B > 65535 || E < 1 || N < 1) return fail(T2H_ERR_ARG, "index_transpose: bad shape B=%d E=%d N=%d", B, E, N);
+    hipStream_t s = as_stream(stream);
+    const long long *src = reinterpret_cast<const long long *>(idx);
+    if (hipMemsetAsync(cursor, 0, (size_t)B * N * sizeof(int32_t), s) != hipSuccess) return fail(T2H_ERR_LAUNCH, "index_transpose: memset");
+    hipLaunchKernelGGL(transpose_count_kernel, dim3(blocks_for(E, 256), B), dim3(256), 0, s, src, E, N, cursor);
+    hipLaunchKernelGGL(transpose_scan_kernel, dim3(B), dim3(256), 0, s, N, offsets, cursor);
+    hipLaunchKernelGGL(transpose_place_kernel, dim3(blocks_for(E, 256), B), dim3(256), 0, s, src, E, N, cursor, entries);
+    hipLaunchKernelGGL(transpose_sort_kernel, dim3(N, B), dim3(256), 0, s, src, E, N, offsets, entries);
+    note_kernel("transpose_sort_kernel");
+    return check_launch("index_transpose");
+}
+
+T2H_API int t2h_rows_gather_bwd(const float *g, int gld, int col0, int D, const float *weight, int fan, const int32_t *offsets,
+                                const int32_t *entries, int B, int E, int N, float *out, t2h_stream_t stream) {
+    if (!g || !offsets || !entries || !out) return fail(T2H_ERR_ARG, "rows_gather_bwd: null pointer");
+    if (fan != 1 && fan != 3) return fail(T2H_ERR_ARG, "rows_gather_bwd: fan=%d must be 1 or 3", fan);
+    if (B < 1 || B > 65535 || E < 1 || N < 1 || D < 1 || D > 64 * 65535 || col0 < 0 || gld < col0 + D || E % fan != 0)
+        return fail(T2H_ERR_ARG, "rows_gather_bwd: bad shape B=%d E=%d N=%d D=%d col0=%d gld=%d fan=%d", B, E, N, D, col0, gld, fan);
+    hipLaunchKernelGGL(rows_gather_bwd_kernel, dim3(N, B, blocks_for(D, 64)), dim3(64, kGatherWaves), 0, as_stream(stream), g, gld,
+                       col0, D, weight, fan, offsets, entries, E, N, out);
+    note_kernel("rows_gather_bwd_kernel");
+    return check_launch("rows_gather_bwd");
 }

@@ -1,4 +1,5 @@
-"""PointNetPlusPlus (reference: tomosar2height/encoder/pointnetpp.py:16-173) on the MI355X path, for inference.
+"""PointNetPlusPlus (reference: tomosar2height/encoder/pointnetpp.py:16-173) on the MI355X path: inference, and gradients of
+every parameter in ``eval()`` (fine-tuning with frozen BatchNorm statistics).
 
 Constructor arguments, ``state_dict`` keys and shapes are the reference's (``sa{1,2,3}`` / ``fp{3,2,1}`` with ``mlp_convs.{k}`` and
 ``mlp_bns.{k}``, BatchNorm buffers and ``num_batches_tracked`` included, ``unet.*``), so a reference checkpoint loads with
@@ -7,8 +8,13 @@ runs on csrc/pnpp.hip (``pointops``); every 1 x 1 ``Conv2d`` / ``Conv1d`` + Batc
 the fp32 MFMA kernels (``mlp.linear_fwd_`` with ``relu_out``) with the BatchNorm running statistics folded into weight and
 bias; rasterisation and the ALTO / plain U-Net are the modules the default encoder uses.
 
-Inference only.  ``forward`` under ``train()`` raises: BatchNorm batch statistics and the backward of the point stages are not
-built (DESIGN.md sections 4.9 and 8).  In ``eval()`` the point stages produce no autograd graph.
+``eval()`` only.  ``forward`` under ``train()`` raises: BatchNorm batch statistics are not built (DESIGN.md sections 4.9 and 8).
+In ``eval()`` with gradients enabled and an encoder parameter (or an incoming feature) that requires one, the stages build an
+autograd graph: the layers run on the same products forward (``_Chain``: ``linear_dgrad_`` / ``linear_wgrad_`` backward, the
+ReLU masks fused into the data gradients), the grouped max, the grouped rows and the 3-NN propagation have their adjoints in
+csrc/pnpp.hip, and the gradients of ``conv.weight``, ``conv.bias``, ``bn.weight`` and ``bn.bias`` follow from the fold's chain
+rule; the running statistics and ``xyz`` get none.  The forward is bit-identical in both modes.  Under ``torch.no_grad()``, or
+with nothing requiring a gradient, the cached fold is used and nothing is saved.
 
 The reference's inference is itself random: ``farthest_point_sample`` starts from ``torch.randint`` (pointnetpp.py:232), once
 for ``sa1`` and once for ``sa2``.  ``fps_start = None`` (default) does the same on the device, in that order -- reproducible
@@ -64,16 +70,87 @@ class _FoldedLayers(nn.Module):
         sources = [t for conv, bn in pairs for t in (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)]
         return self.__dict__["_fold"].get("layers", sources, fold)
 
-    def _chain(self, rows):
-        """relu(bn(conv(.))) of every layer over [M, K] rows."""
+    def folded_graph(self):
+        """The fold as float64 torch operations under autograd, rounded once: the same bytes as ``folded()``, with the chain
+        rule to ``conv.weight``, ``conv.bias``, ``bn.weight`` and ``bn.bias`` (the running statistics are constants)."""
+        layers = []
+        for conv, bn in zip(self.mlp_convs, self.mlp_bns):
+            _lib.require_device(conv.weight, what="PointNetPlusPlus layer")
+            s = bn.weight.double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
+            w = conv.weight.reshape(conv.weight.shape[0], -1).double() * s[:, None]
+            b = (conv.bias.double() - bn.running_mean.detach().double()) * s + bn.bias.double()
+            k = w.shape[1]
+            layers.append((torch.nn.functional.pad(w.float(), (0, _pad4(k) - k)), b.float()))
+        return layers
+
+    def wants_graph(self, *features) -> bool:
+        """True when this stage has to build an autograd graph: gradients are enabled and a parameter of its layers, or a
+        feature tensor it is handed, requires one."""
+        if not torch.is_grad_enabled():
+            return False
+        return any(t is not None and t.requires_grad for t in features) or any(
+            p.requires_grad for m in (self.mlp_convs, self.mlp_bns) for p in m.parameters())
+
+    def _chain(self, rows, nsample=0, graph=False):
+        """relu(bn(conv(.))) of every layer over [M, K] rows; ``nsample`` > 0: followed by the max over each group of
+        ``nsample`` consecutive rows.  ``graph``: as one autograd node (``_Chain``)."""
+        if graph:
+            widths = [conv.weight.shape[0] for conv in self.mlp_convs]
+            if any(w % 4 for w in widths):
+                raise NotImplementedError(f"PointNetPlusPlus gradients need layer widths that are multiples of 4 (16-byte rows of "
+                                          f"the data- and weight-gradient products), got {widths}; inference takes any width")
+            return _Chain.apply(rows, nsample, *[t for wb in self.folded_graph() for t in wb])
         with torch.no_grad():
             for w, b in self.folded():
                 y = torch.empty(rows.shape[0], w.shape[0], dtype=torch.float32, device=rows.device)
                 mlp.linear_fwd_(rows, w, b, y, relu_out=True)
                 rows = y
+            if nsample:
+                rows = pointops.group_max_rows(rows, nsample)
         return rows
 
 
+class _Chain(torch.autograd.Function):
+    """The layers of a stage, y_k = relu(y_{k-1} W'_k^T + b'_k), and (``nsample`` > 0) the max over each group of rows, as one
+    node.  Backward: the gradient of the last pre-activation comes from ``t2h_group_max_bwd(relu=1)`` (set abstraction: max
+    and ReLU mask in one pass) or ``t2h_relu_mask`` (propagation); then per layer ``linear_wgrad_`` over the padded rows and
+    ``linear_dgrad_`` with the layer's input as mask -- the ReLU mask of layer k - 1 is the ``x > 0`` mask of layer k's data
+    gradient.  The first layer's input is data or another node's output: no mask, and no product unless it wants a gradient."""
+
+    @staticmethod
+    def forward(ctx, rows, nsample, *wb):
+        acts = [rows]
+        for w, b in zip(wb[0::2], wb[1::2]):
+            y = torch.empty(rows.shape[0], w.shape[0], dtype=torch.float32, device=rows.device)
+            mlp.linear_fwd_(acts[-1], w, b, y, relu_out=True)
+            acts.append(y)
+        out = pointops._group_max_rows(acts[-1], nsample, acts[-1].shape[1]) if nsample else acts[-1]
+        ctx.nsample, ctx.layers = nsample, len(wb) // 2
+        ctx.save_for_backward(*acts, *wb[0::2], *((out,) if nsample else ()))
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        n = ctx.layers
+        saved = ctx.saved_tensors
+        acts, ws = saved[:n + 1], saved[n + 1:2 * n + 1]
+        gout = gout.contiguous()
+        if ctx.nsample:
+            g = pointops.group_max_bwd(acts[n], saved[-1], gout, ctx.nsample, relu=True)
+        else:
+            g = torch.empty_like(gout)
+            _lib.call("t2h_relu_mask", _lib.ptr(gout), _lib.ptr(acts[n]), _lib.ptr(g), gout.numel(), _lib.stream(),
+                      nbytes=12 * gout.numel())
+        grads = [None] * (2 * n)
+        for k in range(n - 1, -1, -1):
+            x, w = acts[k], ws[k]
+            if ctx.needs_input_grad[2 + 2 * k] or ctx.needs_input_grad[3 + 2 * k]:
+                dw, db = torch.empty_like(w), torch.empty(w.shape[0], dtype=torch.float32, device=w.device)
+                mlp.linear_wgrad_(g, x, dw, db)
+                grads[2 * k], grads[2 * k + 1] = dw, db
+            if k > 0 or ctx.needs_input_grad[0]:
+                g = mlp.linear_dgrad_(g, w, torch.empty_like(x), mask=x if k > 0 else None)
+        return (g if ctx.needs_input_grad[0] else None, None, *grads)
 class PointNetSetAbstraction(_FoldedLayers):
     def __init__(self, npoint, radius, nsample, in_channel, mlp, group_all):
         super().__init__()
@@ -84,30 +161,32 @@ class PointNetSetAbstraction(_FoldedLayers):
         """Point-major form of pointnetpp.py:31-57: ``xyz`` [B, N, 3], ``points`` [B, N, D] or None -> new_xyz [B, S, 3],
         new_points [B, S, D'].  ``trace``: a dict that receives ``fps_idx`` and the ball ``idx``."""
         if self.training:
-            raise NotImplementedError("PointNetSetAbstraction runs in eval() only: BatchNorm batch statistics and the backward "
-                                      "of the point stages are not built")
+            raise NotImplementedError("PointNetSetAbstraction runs in eval() only: BatchNorm batch statistics are not built")
         pointops._cloud(xyz, "PointNetSetAbstraction xyz")
         b, n, _ = xyz.shape
         d = 0 if points is None else points.shape[2]
         ld = _pad4(3 + d)
+        graph = self.wants_graph(points)
         with torch.no_grad():
             if self.group_all:                                             # pointnetpp.py:303-320: a view and a concatenation
                 new_xyz = torch.zeros(b, 1, 3, dtype=torch.float32, device=xyz.device)
-                rows = torch.zeros(b * n, ld, dtype=torch.float32, device=xyz.device)
-                rows[:, :3] = xyz.reshape(b * n, 3)
-                if points is not None:
-                    rows[:, 3:3 + d] = points.reshape(b * n, d)
                 nsample = n
             else:
                 fps_idx = pointops.farthest_point_sample(xyz, self.npoint, start)
                 new_xyz = pointops.index_points(xyz, fps_idx).contiguous()
                 idx = pointops.query_ball_point(self.radius, self.nsample, xyz, new_xyz)
-                rows = pointops.group_rows(xyz, new_xyz, points, idx, ld)
                 nsample = self.nsample
                 if trace is not None:
                     trace["fps_idx"], trace["idx"] = fps_idx, idx
-            feat = self._chain(rows)
-            new_points = pointops.group_max_rows(feat, nsample)
+        with torch.set_grad_enabled(graph):
+            if self.group_all:                                             # (its backward: a column slice)
+                parts = [xyz.reshape(b * n, 3)] + ([] if points is None else [points.reshape(b * n, d)])
+                if ld > 3 + d:
+                    parts.append(torch.zeros(b * n, ld - 3 - d, dtype=torch.float32, device=xyz.device))
+                rows = torch.cat(parts, dim=1)
+            else:
+                rows = pointops.group_rows(xyz, new_xyz, points, idx, ld)
+            new_points = self._chain(rows, nsample, graph)
         return new_xyz, new_points.view(b, -1, new_points.shape[1])
 
     def forward(self, xyz, points, start=None):
@@ -126,17 +205,17 @@ class PointNetFeaturePropagation(_FoldedLayers):
         """Point-major form of pointnetpp.py:70-109: targets ``xyz1`` [B, N, 3] (features ``points1`` [B, N, D1] or None), sources
         ``xyz2`` [B, S, 3] with ``points2`` [B, S, D2] -> [B, N, D'].  ``trace`` receives the 3-NN ``idx`` and ``weight``."""
         if self.training:
-            raise NotImplementedError("PointNetFeaturePropagation runs in eval() only: BatchNorm batch statistics and the "
-                                      "backward of the point stages are not built")
+            raise NotImplementedError("PointNetFeaturePropagation runs in eval() only: BatchNorm batch statistics are not built")
         b, n, _ = xyz1.shape
-        with torch.no_grad():
+        graph = self.wants_graph(points1, points2)
+        with torch.set_grad_enabled(graph):
             interp, idx, weight = pointops.three_nn_interpolate(xyz1, xyz2, points2)
             if trace is not None:
                 trace["idx"], trace["weight"], trace["interpolated"] = idx, weight, interp
             rows = interp.view(b * n, -1)
             if points1 is not None:
                 rows = torch.cat([points1.reshape(b * n, -1), rows], dim=1)
-            out = self._chain(rows)
+            out = self._chain(rows, 0, graph)
         return out.view(b, n, -1)
 
     def forward(self, xyz1, xyz2, points1, points2):
@@ -197,8 +276,8 @@ class PointNetPlusPlus(nn.Module):
     def forward(self, xyz: torch.Tensor, trace: dict = None) -> Dict[str, torch.Tensor]:
         """``xyz`` [B, N, dim] in [0, 1) -> ``{'xy': [B, feature_dim, R, R]}``."""
         if self.training:
-            raise NotImplementedError("PointNetPlusPlus runs in eval() only: training needs BatchNorm batch statistics and the "
-                                      "backward of farthest point sampling, grouping and 3-NN propagation, which are not built")
+            raise NotImplementedError("PointNetPlusPlus runs in eval() only: training needs BatchNorm batch statistics, which are "
+                                      "not built; gradients of every parameter are available in eval() (frozen statistics)")
         pointops._cloud(xyz, "PointNetPlusPlus", cols=None)
         xyz = xyz.contiguous()
         b, n, dim = xyz.shape

@@ -2,8 +2,11 @@
 point sampling, radius grouping, grouped rows, grouped max and 3-nearest-neighbour interpolation over csrc/pnpp.hip.
 
 Argument order and result shapes are the reference's; tensors are point-major (``[B, N, C]``), as the reference's helpers take
-them.  Forward only: results carry no autograd graph.  There is no CPU path: a tensor that is not on
-the device raises.
+them.  ``group_rows``, ``group_max`` / ``group_max_rows`` and ``three_nn_interpolate`` are autograd functions, differentiable in
+their FEATURES (``points``, ``rows``, ``points2``); ``xyz`` is input data, so sampling, grouping, the 3-NN indices and the 3-NN
+weights carry no gradient.  The adjoint of a gather is a sum over an inverted index
+(``index_transpose``), in a fixed association and without a float atomic: two backward passes give the same bytes.  There is
+no CPU path: a tensor that is not on the device raises.
 
 Squared distances are taken by differences in fp32, ``(dx*dx + dy*dy) + dz*dz``; the reference's matmul form rounds
 differently within a few ulps of 6 at unit coordinates, which can move a point that lies that close to a ball's boundary, or
@@ -30,6 +33,9 @@ SIGNATURES = {
     "t2h_group_rows": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "t2h_group_max": (_i, [_vp, _i, _i64, _i, _i, _vp, _vp]),
     "t2h_three_nn_interp": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "t2h_group_max_bwd": (_i, [_vp, _i, _i64, _i, _i, _vp, _vp, _i, _vp, _i, _vp]),
+    "t2h_index_transpose": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "t2h_rows_gather_bwd": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
 }
 
 FPS_ONE_WG_MAX = 2048       # T2H_FPS_ONE_WG_MAX
@@ -117,17 +123,79 @@ def query_ball_point(radius: float, nsample: int, xyz: torch.Tensor, new_xyz: to
     return idx
 
 
-def group_rows(xyz, new_xyz, points, idx, ld=None) -> torch.Tensor:
-    """Rows [B * S * nsample, ld] = grouped xyz minus the centroid | grouped features | zeros (``ld`` >= 3 + D: the row length
-    the layers' products want, a multiple of 4)."""
+def _group_rows(xyz, new_xyz, points, idx, ld):
     b, n, _ = xyz.shape
     _, s, ns = idx.shape
     d = 0 if points is None else points.shape[2]
-    ld = 3 + d if ld is None else ld
     rows = torch.empty(b * s * ns, ld, dtype=torch.float32, device=xyz.device)
     _lib.call("t2h_group_rows", _lib.ptr(xyz), _lib.ptr(new_xyz), None if points is None else _lib.ptr(points), _lib.ptr(idx), b, n,
               s, ns, d, ld, _lib.ptr(rows), _lib.stream(), nbytes=b * s * ns * (8 + 4 * (3 + d) + 4 * ld))
     return rows
+
+
+def index_transpose(idx: torch.Tensor, n: int):
+    """The inverted index of ``idx`` [B, ...] int64 over ``n`` sources (t2h_index_transpose): ``offsets`` [B, n + 1] int32 and
+    ``entries`` [B, E] int32, per cloud the stable argsort of the flattened ``idx``; an index outside [0, n) counts as n - 1."""
+    _lib.require_device(idx, what="index_transpose")
+    if idx.dtype != torch.long or idx.dim() < 2:
+        raise ValueError(f"index_transpose: expected an int64 [B, ...] tensor, got {idx.dtype} {tuple(idx.shape)}")
+    b = idx.shape[0]
+    e = idx.numel() // b
+    offsets = torch.empty(b, n + 1, dtype=torch.int32, device=idx.device)
+    entries = torch.empty(b, e, dtype=torch.int32, device=idx.device)
+    cursor = torch.empty(b, n, dtype=torch.int32, device=idx.device)          # scratch: [B, n] int32 (include/t2h_pnpp.h)
+    _lib.call("t2h_index_transpose", _lib.ptr(idx), b, e, n, _lib.ptr(offsets), _lib.ptr(entries), _lib.ptr(cursor), _lib.stream(),
+              nbytes=b * (3 * 8 * e + 4 * e + 12 * n))
+    return offsets, entries
+
+
+def rows_gather_bwd(g: torch.Tensor, col0: int, d: int, weight, fan: int, offsets, entries, n: int) -> torch.Tensor:
+    """out [B, n, d] = per source the sum, over the positions that read it, of ``weight`` x columns ``col0 .. col0 + d`` of the
+    rows ``g`` [B * E / fan, >= col0 + d] (t2h_rows_gather_bwd; ``g`` may be a column slice of wider rows)."""
+    _lib.require_device(offsets, entries, weight, what="rows_gather_bwd")
+    if g.dim() != 2 or g.dtype != torch.float32 or g.stride(1) != 1:
+        raise ValueError("rows_gather_bwd: expected fp32 rows with unit column stride")
+    b, e = entries.shape
+    if g.shape[0] * fan != b * e or g.shape[1] < col0 + d:
+        raise ValueError(f"rows_gather_bwd: {tuple(g.shape)} rows for {b} x {e} entries at fan {fan}, columns {col0} .. {col0 + d}")
+    out = torch.empty(b, n, d, dtype=torch.float32, device=g.device)
+    _lib.call("t2h_rows_gather_bwd", _lib.ptr(g), g.stride(0), col0, d, None if weight is None else _lib.ptr(weight), fan,
+              _lib.ptr(offsets), _lib.ptr(entries), b, e, n, _lib.ptr(out), _lib.stream(),
+              nbytes=b * e * (4 * d + 8) + 4 * b * n * d, flops=2 * b * e * d)
+    return out
+
+
+def _row_slice(g: torch.Tensor) -> torch.Tensor:
+    """``g`` [..., d] as 2-D rows the kernels can read in place: a column slice of contiguous rows stays a view."""
+    g2 = g.reshape(-1, g.shape[-1]) if g.dim() != 2 else g
+    if g2.stride(1) != 1 or g2.stride(0) < g2.shape[1]:
+        g2 = g2.contiguous()
+    return g2
+
+
+class _GroupRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, points, xyz, new_xyz, idx, ld):
+        ctx.save_for_backward(idx)
+        ctx.n, ctx.d = points.shape[1], points.shape[2]
+        return _group_rows(xyz, new_xyz, points, idx, ld)
+
+    @staticmethod
+    def backward(ctx, grows):
+        idx, = ctx.saved_tensors
+        offsets, entries = index_transpose(idx, ctx.n)          # built here: only when ``points`` wants a gradient
+        return rows_gather_bwd(_row_slice(grows), 3, ctx.d, None, 1, offsets, entries, ctx.n), None, None, None, None
+
+
+def group_rows(xyz, new_xyz, points, idx, ld=None) -> torch.Tensor:
+    """Rows [B * S * nsample, ld] = grouped xyz minus the centroid | grouped features | zeros (``ld`` >= 3 + D: the row length
+    the layers' products want, a multiple of 4).  Differentiable in ``points``: the gradient is the sum, per point, of the rows
+    that gathered it (columns 3 .. 3 + D), over the transpose of ``idx``, which is built in the backward pass."""
+    d = 0 if points is None else points.shape[2]
+    ld = 3 + d if ld is None else ld
+    if points is None or not (torch.is_grad_enabled() and points.requires_grad):
+        return _group_rows(xyz, new_xyz, points, idx, ld)
+    return _GroupRows.apply(points, xyz, new_xyz, idx, ld)
 
 
 def sample_and_group(npoint, radius, nsample, xyz, points, returnfps=False, start=None):
@@ -147,15 +215,49 @@ def sample_and_group(npoint, radius, nsample, xyz, points, returnfps=False, star
     return new_xyz, new_points
 
 
-def group_max_rows(rows: torch.Tensor, nsample: int, c: int = None) -> torch.Tensor:
-    """[groups * nsample, ld] rows -> [groups, c]: the max over each group's rows (columns 0 .. c)."""
-    _lib.require_device(rows, what="group_max")
-    c = rows.shape[1] if c is None else c
+def _group_max_rows(rows, nsample, c):
     groups = rows.shape[0] // nsample
     out = torch.empty(groups, c, dtype=torch.float32, device=rows.device)
     _lib.call("t2h_group_max", _lib.ptr(rows), rows.stride(0), groups, nsample, c, _lib.ptr(out), _lib.stream(),
               nbytes=4 * c * (rows.shape[0] + groups))
     return out
+
+
+def group_max_bwd(rows, out, gout, nsample: int, relu: bool = False, gld: int = None) -> torch.Tensor:
+    """Gradient of the rows [groups * nsample, gld] of ``group_max_rows`` (t2h_group_max_bwd): ``gout`` goes to the lowest row
+    of each group that holds the maximum ``out``, +0 elsewhere; ``relu``: +0 also in every column whose maximum is not positive
+    (the mask of a ReLU applied to the rows before the max)."""
+    _lib.require_device(rows, out, gout, what="group_max_bwd")
+    groups, c = out.shape
+    gld = c if gld is None else gld
+    grows = torch.empty(groups * nsample, gld, dtype=torch.float32, device=rows.device)
+    _lib.call("t2h_group_max_bwd", _lib.ptr(rows), rows.stride(0), groups, nsample, c, _lib.ptr(out), _lib.ptr(gout), int(bool(relu)),
+              _lib.ptr(grows), gld, _lib.stream(), nbytes=4 * groups * (nsample * (c + gld) + 2 * c))
+    return grows
+
+
+class _GroupMax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rows, nsample, c):
+        out = _group_max_rows(rows, nsample, c)
+        ctx.save_for_backward(rows, out)
+        ctx.nsample = nsample
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        rows, out = ctx.saved_tensors
+        return group_max_bwd(rows, out, gout.contiguous(), ctx.nsample, gld=rows.shape[1]), None, None
+
+
+def group_max_rows(rows: torch.Tensor, nsample: int, c: int = None) -> torch.Tensor:
+    """[groups * nsample, ld] rows -> [groups, c]: the max over each group's rows (columns 0 .. c).  Differentiable in ``rows``:
+    the lowest row that holds the maximum takes the gradient."""
+    _lib.require_device(rows, what="group_max")
+    c = rows.shape[1] if c is None else c
+    if torch.is_grad_enabled() and rows.requires_grad:
+        return _GroupMax.apply(rows, nsample, c)
+    return _group_max_rows(rows, nsample, c)
 
 
 def group_max(new_points: torch.Tensor) -> torch.Tensor:
@@ -167,20 +269,43 @@ def group_max(new_points: torch.Tensor) -> torch.Tensor:
     return group_max_rows(new_points.view(b * s * ns, c), ns).view(b, s, c)
 
 
-def three_nn_interpolate(xyz1: torch.Tensor, xyz2: torch.Tensor, points2: torch.Tensor):
-    """pointnetpp.py:87-97: features ``points2`` [B, S, D] at ``xyz2`` [B, S, 3] interpolated to ``xyz1`` [B, N, 3] with
-    inverse-square-distance weights over the three nearest sources -> (interpolated [B, N, D], idx [B, N, 3] int64, weight
-    [B, N, 3]).  ``S == 1`` repeats the one source row (idx 0, weight 1, 0, 0)."""
-    _cloud(xyz1, "three_nn_interpolate xyz1")
-    _cloud(xyz2, "three_nn_interpolate xyz2")
-    _cloud(points2, "three_nn_interpolate points2", cols=None)
+def _three_nn_interpolate(xyz1, xyz2, points2):
     b, n, _ = xyz1.shape
     s, d = xyz2.shape[1], points2.shape[2]
-    if points2.shape[:2] != xyz2.shape[:2] or xyz2.shape[0] != b:
-        raise ValueError("three_nn_interpolate: xyz2 and points2 must share [B, S]")
     idx = torch.empty(b, n, 3, dtype=torch.long, device=xyz1.device)
     weight = torch.empty(b, n, 3, dtype=torch.float32, device=xyz1.device)
     out = torch.empty(b, n, d, dtype=torch.float32, device=xyz1.device)
     _lib.call("t2h_three_nn_interp", _lib.ptr(xyz1), _lib.ptr(xyz2), _lib.ptr(points2), b, n, s, d, _lib.ptr(idx), _lib.ptr(weight),
               _lib.ptr(out), _lib.stream(), nbytes=b * n * (12 + 36 + 16 * d) + b * s * 12, flops=b * n * (9 * s + 5 * d))
     return out, idx, weight
+
+
+class _ThreeNN(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, points2, xyz1, xyz2):
+        out, idx, weight = _three_nn_interpolate(xyz1, xyz2, points2)
+        ctx.mark_non_differentiable(idx, weight)
+        ctx.save_for_backward(idx, weight)
+        ctx.s = points2.shape[1]
+        return out, idx, weight
+
+    @staticmethod
+    def backward(ctx, gout, _gidx, _gweight):
+        idx, weight = ctx.saved_tensors
+        offsets, entries = index_transpose(idx, ctx.s)
+        return rows_gather_bwd(_row_slice(gout), 0, gout.shape[-1], weight, 3, offsets, entries, ctx.s), None, None
+
+
+def three_nn_interpolate(xyz1: torch.Tensor, xyz2: torch.Tensor, points2: torch.Tensor):
+    """pointnetpp.py:87-97: features ``points2`` [B, S, D] at ``xyz2`` [B, S, 3] interpolated to ``xyz1`` [B, N, 3] with
+    inverse-square-distance weights over the three nearest sources -> (interpolated [B, N, D], idx [B, N, 3] int64, weight
+    [B, N, 3]).  ``S == 1`` repeats the one source row (idx 0, weight 1, 0, 0).  Differentiable in ``points2`` (per source the
+    weighted sum of the target rows that read it); ``idx`` and ``weight`` never require a gradient."""
+    _cloud(xyz1, "three_nn_interpolate xyz1")
+    _cloud(xyz2, "three_nn_interpolate xyz2")
+    _cloud(points2, "three_nn_interpolate points2", cols=None)
+    if points2.shape[:2] != xyz2.shape[:2] or xyz2.shape[0] != xyz1.shape[0]:
+        raise ValueError("three_nn_interpolate: xyz2 and points2 must share [B, S]")
+    if torch.is_grad_enabled() and points2.requires_grad:
+        return _ThreeNN.apply(points2, xyz1, xyz2)
+    return _three_nn_interpolate(xyz1, xyz2, points2)
