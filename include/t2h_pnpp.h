@@ -3,7 +3,8 @@
  * reference's tomosar2height/encoder/pointnetpp.py (farthest_point_sample :220-241, query_ball_point :244-264,
  * sample_and_group :279-296, torch.max(new_points, 2) :55, PointNetFeaturePropagation.forward :90-97), and the adjoints of the
  * grouped rows, the grouped max and the propagation with respect to the FEATURES (xyz is input data: sampling, grouping, the
- * 3-NN indices and weights have no gradient).  The encoder built on them runs in eval().
+ * 3-NN indices and weights have no gradient).  The t2h_bn_* entries are BatchNorm in training mode over
+ * the layers' rows: batch statistics, their backward and the running averages.
  *
  * Same conventions as t2h.h: device pointers owned by the caller, no allocation, no state, stream-ordered calls, 0 or a
  * negative T2H_ERR_* code, every argument validated before any launch.  The entries live in the same library but are typed by
@@ -109,6 +110,52 @@ int t2h_index_transpose(const int64_t *idx, int B, int E, int N, int32_t *offset
  * 64 columns, one lane per column. */
 int t2h_rows_gather_bwd(const float *g, int gld, int col0, int D, const float *weight, int fan, const int32_t *offsets,
                         const int32_t *entries, int B, int E, int N, float *out, t2h_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------- BatchNorm batch statistics */
+#define T2H_BN_SLAB 256             /* rows per slab of the column reductions */
+#define T2H_BN_WAVES 4              /* interleaved row sums per slab and column */
+
+/* nn.BatchNorm2d / BatchNorm1d in training mode over the rows layout: the [B, C, nsample, S] / [B, C, N] reduction is the
+ * reduction over the M rows of z [M, ld] fp32, per column c < C <= ld.  2 <= M <= 2^24 (M is used as an exact float; one value
+ * per channel has no variance: torch raises, these entries refuse M < 2).  Every operation below is rounded once in fp32, no
+ * fused multiply-add, no float atomic; launch boundaries are the only synchronisation.
+ *
+ * Association of a COLUMN SUM of terms t[r], the same for every reduction here: the rows are cut into slabs of T2H_BN_SLAB
+ * consecutive rows, slab k = rows 256 k ..; lane sum w of T2H_BN_WAVES starts from +0 and adds the slab's terms of rows
+ * 256 k + w, 256 k + w + 4, ... in ascending order; the slab's partial is ((lane_0 + lane_1) + lane_2) + lane_3; the column sum
+ * starts from +0 and adds the slab partials in ascending k (a second launch).  `partial` is scratch of
+ * ceil(M / T2H_BN_SLAB) * C floats (t2h_bn_bwd_reduce: twice that), any contents, overwritten.
+ *
+ * t2h_bn_col_stats, two passes (never E[z^2] - E[z]^2):  mean[c] = (column sum of z) / M;
+ *   var[c] = (column sum of d * d, d = z - mean[c]) / M   (the biased variance);   rstd[c] = 1 / sqrt(var[c] + eps)
+ *   (an addition, a correctly rounded square root, a correctly rounded division); 1e-30 <= eps <= 1e30. */
+int t2h_bn_col_stats(const float *z, int ld, int M, int C, float eps, float *partial, float *mean, float *var, float *rstd,
+                     t2h_stream_t stream);
+
+/* y [M, ldy]: y[r, c] = max(z[r, c] * s + t, 0) with s = gamma[c] * rstd[c], t = beta[c] - mean[c] * s (a product, then a sum,
+ * then the max); columns C .. ldy are +0 (the next product reads padded rows). */
+int t2h_bn_apply_relu(const float *z, int ldz, int M, int C, const float *mean, const float *rstd, const float *gamma,
+                      const float *beta, float *y, int ldy, t2h_stream_t stream);
+
+/* running_mean = (1 - momentum) * running_mean + momentum * mean;
+ * running_var  = (1 - momentum) * running_var  + momentum * (var * (M / (M - 1)))   in place, per column; (1 - momentum) and
+ * M / (M - 1) are fp32 values, each side of the sum a rounded product.  num_batches_tracked is the caller's. */
+int t2h_bn_running_update(const float *mean, const float *var, int M, int C, float momentum, float *running_mean,
+                          float *running_var, t2h_stream_t stream);
+
+/* Backward of y = [relu](gamma * xhat + beta), xhat = (z - mean) * rstd, given gy [M, ldg] = the gradient of y.
+ * g = gy where relu == 0; relu != 0: g = gy & -(y > 0) (the bits of gy where y[r, c] > 0, +0 elsewhere; y [M, ldy] may be NULL
+ * with relu == 0 -- the last layer of a set abstraction, where t2h_group_max_bwd(relu = 1) has applied the mask).
+ * t2h_bn_bwd_reduce: dbeta[c] = column sum of g, dgamma[c] = column sum of g * xhat (xhat = (z - mean) * rstd: a difference, a
+ *   product; then the product with g), in the association above. */
+int t2h_bn_bwd_reduce(const float *gy, int ldg, const float *y, int ldy, const float *z, int ldz, int M, int C, const float *mean,
+                      const float *rstd, int relu, float *partial, float *dbeta, float *dgamma, t2h_stream_t stream);
+
+/* dz [M, gld]: dz[r, c] = a * ((g - mb) - xhat * mg) with a = gamma[c] * rstd[c], mb = dbeta[c] / M, mg = dgamma[c] / M;
+ * columns C .. gld are +0. */
+int t2h_bn_bwd_apply(const float *gy, int ldg, const float *y, int ldy, const float *z, int ldz, int M, int C, const float *mean,
+                     const float *rstd, const float *gamma, const float *dbeta, const float *dgamma, int relu, float *dz, int gld,
+                     t2h_stream_t stream);
 
 #ifdef __cplusplus
 }

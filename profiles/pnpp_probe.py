@@ -2,6 +2,8 @@
 
     python profiles/pnpp_probe.py [--out FILE, default profiles/r12_pnpp.txt] [--points 131072] [--repeats 10] [--warmup 3]
     python profiles/pnpp_probe.py --reference          # on a host that holds the reference tree: its encoder forward on the CPU
+    python profiles/pnpp_probe.py --batch-statistics   # train() with BatchNorm batch statistics: forward, forward + backward
+                                                       # (default --out profiles/pnpp_train_probe.txt)
 
 N = 131 072, B = 1, plane resolution 256, ALTO depth 5, feature_dim 32.  HIP events around every stage of the point side on its
 real inputs and around the whole encoder forward, after a warm-up; the launches of one forward.  Every step runs under a time
@@ -156,16 +158,58 @@ def device(args):
     write(args.out, lines, keep_host=True)
 
 
+def batch_statistics(args):
+    """The encoder under train() with the opt-in batch statistics: forward under no_grad, forward with the graph, and forward +
+    backward of L = sum(plane), every parameter of the encoder requiring a gradient."""
+    from tomosar2height_amd.encoder.pointnetpp import PointNetPlusPlus
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    enc = PointNetPlusPlus(**KW, batch_statistics=True).to(dev).train()
+    enc.set_channels_last(True)
+    enc.fps_start = 0
+    pts = cloud(args.points).to(dev)
+    rows = []
+
+    def stage(name, fn):
+        with step(name, args.limit):
+            _, ms = timed(fn, args.warmup, args.repeats)
+        rows.append(f"{name:52s}: {fmt(ms)}")
+        print(rows[-1], flush=True)
+
+    def no_grad():
+        with torch.no_grad():
+            return enc(pts)["xy"]
+
+    def fwd_bwd():
+        enc.zero_grad(set_to_none=True)
+        enc(pts)["xy"].sum().backward()
+
+    stage("train() forward, no_grad (statistics + updates)", no_grad)
+    stage("train() forward with the autograd graph", lambda: enc(pts)["xy"])
+    stage("train() forward + backward", fwd_bwd)
+    enc.eval()
+    stage("eval() forward, no_grad (folded, for comparison)", no_grad)
+    lines = [f"PointNet++ encoder, BatchNorm batch statistics: N = {args.points}, B = 1, resolution 256, ALTO depth 5",
+             f"device: {torch.cuda.get_device_name(0)}; warm-up {args.warmup}, repeats {args.repeats}, HIP events"] + rows
+    write(args.out, lines, keep_host=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r12_pnpp.txt"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--points", type=int, default=131072)
     ap.add_argument("--repeats", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--limit", type=int, default=120, help="seconds per step")
     ap.add_argument("--reference", action="store_true", help="time the reference's encoder forward on the host CPU instead")
+    ap.add_argument("--batch-statistics", action="store_true", help="time the encoder under train() with batch statistics instead")
     args = ap.parse_args()
-    reference(args) if args.reference else device(args)
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "pnpp_train_probe.txt" if args.batch_statistics else "r12_pnpp.txt")
+    if args.batch_statistics:
+        batch_statistics(args)
+    else:
+        reference(args) if args.reference else device(args)
 
 
 if __name__ == "__main__":

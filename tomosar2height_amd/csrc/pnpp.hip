@@ -45,6 +45,8 @@ constexpr int kNnChunk = 512;
 constexpr int kSortMax = T2H_TRANSPOSE_SORT_MAX;
 constexpr int kGatherChunk = T2H_GATHER_CHUNK;
 constexpr int kGatherWaves = T2H_GATHER_LANES;
+constexpr int kBnSlab = T2H_BN_SLAB;
+constexpr int kBnWaves = T2H_BN_WAVES;
 static_assert(kGatherChunk == 64, "a chunk's entries are held one per lane of a wave");
 static_assert((kSortMax & (kSortMax - 1)) == 0, "the sorting network pads to a power of two");
 
@@ -512,7 +514,140 @@ __global__ __launch_bounds__(64 * kGatherWaves) void rows_gather_bwd_kernel(cons
     }
 }
 
+// ---------------------------------------------------------------------------------------- BatchNorm batch statistics
+// Column reductions over rows [M, ld] in the association of include/t2h_pnpp.h.  grid (slabs, ceil(C / 64)), block (64, kBnWaves):
+// one slab of kBnSlab rows and 64 columns per workgroup, one lane per column (256-byte coalesced row segments).  Wave y adds the
+// terms of the slab's rows y, y + 4, ... in ascending order from +0; the slab's partial is ((w_0 + w_1) + w_2) + w_3.  Row bounds
+// are loop limits, the column is clamped for the loads (v_min) and the store is a branch: no compare feeds a select.
+//   MODE 0: term = z                        MODE 1: term = (z - mean)^2
+//   MODE 2: two sums, g and g * xhat, with g = gy & (-(y > 0) | keep_all) (keep_all: y is any readable rows), xhat = (z - mean) * rstd  (second plane: nslabs * C floats on)
+template <int MODE>
+__global__ __launch_bounds__(64 * kBnWaves) void bn_partial_kernel(const float *__restrict__ z, int ldz, int M, int C,
+                                                                    const float *__restrict__ mean, const float *__restrict__ rstd,
+                                                                    const float *__restrict__ gy, int ldg,
+                                                                    const float *__restrict__ y, int ldy, unsigned keep_all,
+                                                                    float *__restrict__ partial) {
+    __shared__ float wave_sum[MODE == 2 ? 2 : 1][kBnWaves][64];
+    const int c = blockIdx.y * 64 + threadIdx.x, cc = min(c, C - 1), w = threadIdx.y;
+    const int r0 = blockIdx.x * kBnSlab, r1 = min(r0 + kBnSlab, M);
+    float mu = 0.0f, rs = 0.0f;
+    if (MODE >= 1) mu = mean[cc];
+    if (MODE == 2) rs = rstd[cc];
+    float s0 = 0.0f, s1 = 0.0f;
+    for (int r = r0 + w; r < r1; r += kBnWaves) {
+        const float v = z[(size_t)r * ldz + cc];
+        if (MODE == 0) {
+            s0 = __fadd_rn(s0, v);
+        } else if (MODE == 1) {
+            const float d = __fsub_rn(v, mu);
+            s0 = __fadd_rn(s0, __fmul_rn(d, d));
+        } else {
+            const float g = __uint_as_float(__float_as_uint(gy[(size_t)r * ldg + cc]) & (pn_positive_mask(y[(size_t)r * ldy + cc]) | keep_all));
+            s0 = __fadd_rn(s0, g);
+            s1 = __fadd_rn(s1, __fmul_rn(g, __fmul_rn(__fsub_rn(v, mu), rs)));
+        }
+    }
+    wave_sum[0][w][threadIdx.x] = s0;
+    if (MODE == 2) wave_sum[1][w][threadIdx.x] = s1;
+    __syncthreads();
+    if (w == 0 && c < C) {
+        const size_t plane = (size_t)gridDim.x * C;
+#pragma unroll
+        for (int p = 0; p < (MODE == 2 ? 2 : 1); ++p) {
+            float t = wave_sum[p][0][threadIdx.x];
+            for (int k = 1; k < kBnWaves; ++k) t = __fadd_rn(t, wave_sum[p][k][threadIdx.x]);
+            partial[p * plane + (size_t)blockIdx.x * C + c] = t;
+        }
+    }
+}
+
+// Correctly rounded square root of a normal x without a compare: v_sqrt_f32 is within one ulp; its lower neighbour is the
+// result when x - s_dn * s <= 0, its upper one when x - s_up * s > 0 (exact signs from one FMA each) -- the fix-up hipcc's own
+// sqrtf makes with v_cmp + v_cndmask, here as integer steps from the opaque v_med3_i32 mask.
+__device__ inline float bn_sqrt(float x) {
+    const float s = __builtin_amdgcn_sqrtf(x);
+    const int b = __float_as_int(s);
+    const float r_dn = __fmaf_rn(-__int_as_float(b - 1), s, x), r_up = __fmaf_rn(-__int_as_float(b + 1), s, x);
+    return __int_as_float(b + (int)~pn_positive_mask(r_dn) + (int)(pn_positive_mask(r_up) & 1u));
+}
+
+// grid (ceil(C / 256)), one lane per column: the slab partials in ascending slab order from +0, then
+//   mode 0: out0 = mean = sum / M          mode 1: out0 = var = sum / M, out1 = rstd = 1 / sqrt(var + eps)
+//   mode 2: out0 = the first plane's sum, out1 = the second plane's
+__global__ __launch_bounds__(256) void bn_finish_kernel(const float *__restrict__ partial, int nslabs, int C, int mode, float m,
+                                                        float eps, float *__restrict__ out0, float *__restrict__ out1) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    float s0 = 0.0f, s1 = 0.0f;
+    for (int k = 0; k < nslabs; ++k) s0 = __fadd_rn(s0, partial[(size_t)k * C + c]);
+    if (mode == 2) {                                                      // (uniform)
+        for (int k = 0; k < nslabs; ++k) s1 = __fadd_rn(s1, partial[((size_t)nslabs + k) * C + c]);
+        out0[c] = s0;
+        out1[c] = s1;
+        return;
+    }
+    const float q = __fdiv_rn(s0, m);
+    out0[c] = q;
+    if (mode == 1) out1[c] = __fdiv_rn(1.0f, bn_sqrt(__fadd_rn(q, eps)));
+}
+
+// grid (ceil(M / kBnSlab), ceil(ldy / 64)), block (64, kBnWaves): y = max(z * s + t, 0), s = gamma * rstd, t = beta - mean * s
+// (once per lane: its column is fixed); columns C .. ldy are +0.  The max is an opaque v_max_f32.
+__global__ __launch_bounds__(64 * kBnWaves) void bn_apply_relu_kernel(const float *__restrict__ z, int ldz, int M, int C,
+                                                                       const float *__restrict__ mean, const float *__restrict__ rstd,
+                                                                       const float *__restrict__ gamma, const float *__restrict__ beta,
+                                                                       float *__restrict__ y, int ldy) {
+    const int c = blockIdx.y * 64 + threadIdx.x;
+    if (c >= ldy) return;
+    const int r0 = blockIdx.x * kBnSlab, r1 = min(r0 + kBnSlab, M);
+    if (c >= C) {
+        for (int r = r0 + threadIdx.y; r < r1; r += kBnWaves) y[(size_t)r * ldy + c] = 0.0f;
+        return;
+    }
+    const float s = __fmul_rn(gamma[c], rstd[c]), t = __fsub_rn(beta[c], __fmul_rn(mean[c], s));
+    for (int r = r0 + threadIdx.y; r < r1; r += kBnWaves)
+        y[(size_t)r * ldy + c] = pn_max(__fadd_rn(__fmul_rn(z[(size_t)r * ldz + c], s), t), 0.0f);
+}
+
+// same grid: dz = a * ((g - mb) - xhat * mg), a = gamma * rstd, mb = dbeta / M, mg = dgamma / M, xhat = (z - mean) * rstd,
+// g = gy [& (y > 0)]; columns C .. gld are +0
+__global__ __launch_bounds__(64 * kBnWaves) void bn_bwd_apply_kernel(const float *__restrict__ gy, int ldg, const float *__restrict__ y,
+                                                                      int ldy, const float *__restrict__ z, int ldz, int M, int C,
+                                                                      const float *__restrict__ mean, const float *__restrict__ rstd,
+                                                                      const float *__restrict__ gamma, const float *__restrict__ dbeta,
+                                                                      const float *__restrict__ dgamma, float m, unsigned keep_all,
+                                                                      float *__restrict__ dz, int gld) {
+    const int c = blockIdx.y * 64 + threadIdx.x;
+    if (c >= gld) return;
+    const int r0 = blockIdx.x * kBnSlab, r1 = min(r0 + kBnSlab, M);
+    if (c >= C) {
+        for (int r = r0 + threadIdx.y; r < r1; r += kBnWaves) dz[(size_t)r * gld + c] = 0.0f;
+        return;
+    }
+    const float mu = mean[c], rs = rstd[c], a = __fmul_rn(gamma[c], rs);
+    const float mb = __fdiv_rn(dbeta[c], m), mg = __fdiv_rn(dgamma[c], m);
+    for (int r = r0 + threadIdx.y; r < r1; r += kBnWaves) {
+        const unsigned gb = __float_as_uint(gy[(size_t)r * ldg + c]) & (pn_positive_mask(y[(size_t)r * ldy + c]) | keep_all);
+        const float xhat = __fmul_rn(__fsub_rn(z[(size_t)r * ldz + c], mu), rs);
+        dz[(size_t)r * gld + c] = __fmul_rn(a, __fsub_rn(__fsub_rn(__uint_as_float(gb), mb), __fmul_rn(xhat, mg)));
+    }
+}
+
+// one lane per column: the momentum recurrence of the running statistics, with the unbiased variance var * (M / (M - 1))
+__global__ __launch_bounds__(256) void bn_running_kernel(const float *__restrict__ mean, const float *__restrict__ var, int C, float m,
+                                                         float momentum, float *__restrict__ running_mean,
+                                                         float *__restrict__ running_var) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    const float keep = __fsub_rn(1.0f, momentum), unbias = __fdiv_rn(m, __fsub_rn(m, 1.0f));
+    running_mean[c] = __fadd_rn(__fmul_rn(keep, running_mean[c]), __fmul_rn(momentum, mean[c]));
+    running_var[c] = __fadd_rn(__fmul_rn(keep, running_var[c]), __fmul_rn(momentum, __fmul_rn(var[c], unbias)));
+}
+
 static unsigned blocks_for(long long total, int per) { return (unsigned)((total + per - 1) / per); }
+
+// shapes every BatchNorm entry accepts: 2 <= M <= 2^24 (M is exact as a float), 1 <= C <= every row length
+static bool bn_shape_ok(int M, int C) { return M >= 2 && M <= (1 << 24) && C >= 1 && C <= 64 * 65535; }
 
 }  // namespace t2h
 
@@ -637,4 +772,72 @@ T2H_API int t2h_rows_gather_bwd(const float *g, int gld, int col0, int D, const 
                        col0, D, weight, fan, offsets, entries, E, N, out);
     note_kernel("rows_gather_bwd_kernel");
     return check_launch("rows_gather_bwd");
+}
+
+// ---------------------------------------------------------------------------------------- BatchNorm batch statistics
+T2H_API int t2h_bn_col_stats(const float *z, int ld, int M, int C, float eps, float *partial, float *mean, float *var, float *rstd,
+                             t2h_stream_t stream) {
+    if (!z || !partial || !mean || !var || !rstd) return fail(T2H_ERR_ARG, "bn_col_stats: null pointer");
+    if (!bn_shape_ok(M, C) || ld < C) return fail(T2H_ERR_ARG, "bn_col_stats: bad shape M=%d C=%d ld=%d (M >= 2)", M, C, ld);
+    if (!(eps >= 1e-30f && eps <= 1e30f)) return fail(T2H_ERR_ARG, "bn_col_stats: eps=%g outside [1e-30, 1e30]", (double)eps);
+    hipStream_t s = as_stream(stream);
+    const unsigned nslabs = blocks_for(M, kBnSlab);
+    const dim3 grid(nslabs, blocks_for(C, 64)), block(64, kBnWaves);
+    hipLaunchKernelGGL(bn_partial_kernel<0>, grid, block, 0, s, z, ld, M, C, nullptr, nullptr, nullptr, 0, nullptr, 0, 0u, partial);
+    hipLaunchKernelGGL(bn_finish_kernel, dim3(blocks_for(C, 256)), dim3(256), 0, s, partial, (int)nslabs, C, 0, (float)M, eps, mean,
+                       nullptr);
+    hipLaunchKernelGGL(bn_partial_kernel<1>, grid, block, 0, s, z, ld, M, C, mean, nullptr, nullptr, 0, nullptr, 0, 0u, partial);
+    hipLaunchKernelGGL(bn_finish_kernel, dim3(blocks_for(C, 256)), dim3(256), 0, s, partial, (int)nslabs, C, 1, (float)M, eps, var, rstd);
+    note_kernel("bn_partial_kernel");
+    return check_launch("bn_col_stats");
+}
+
+T2H_API int t2h_bn_apply_relu(const float *z, int ldz, int M, int C, const float *mean, const float *rstd, const float *gamma,
+                              const float *beta, float *y, int ldy, t2h_stream_t stream) {
+    if (!z || !mean || !rstd || !gamma || !beta || !y) return fail(T2H_ERR_ARG, "bn_apply_relu: null pointer");
+    if (!bn_shape_ok(M, C) || ldz < C || ldy < C || ldy > 64 * 65535)
+        return fail(T2H_ERR_ARG, "bn_apply_relu: bad shape M=%d C=%d ldz=%d ldy=%d", M, C, ldz, ldy);
+    hipLaunchKernelGGL(bn_apply_relu_kernel, dim3(blocks_for(M, kBnSlab), blocks_for(ldy, 64)), dim3(64, kBnWaves), 0, as_stream(stream),
+                       z, ldz, M, C, mean, rstd, gamma, beta, y, ldy);
+    note_kernel("bn_apply_relu_kernel");
+    return check_launch("bn_apply_relu");
+}
+
+T2H_API int t2h_bn_running_update(const float *mean, const float *var, int M, int C, float momentum, float *running_mean,
+                                  float *running_var, t2h_stream_t stream) {
+    if (!mean || !var || !running_mean || !running_var) return fail(T2H_ERR_ARG, "bn_running_update: null pointer");
+    if (!bn_shape_ok(M, C)) return fail(T2H_ERR_ARG, "bn_running_update: bad shape M=%d C=%d (M >= 2)", M, C);
+    hipLaunchKernelGGL(bn_running_kernel, dim3(blocks_for(C, 256)), dim3(256), 0, as_stream(stream), mean, var, C, (float)M, momentum,
+                       running_mean, running_var);
+    note_kernel("bn_running_kernel");
+    return check_launch("bn_running_update");
+}
+
+T2H_API int t2h_bn_bwd_reduce(const float *gy, int ldg, const float *y, int ldy, const float *z, int ldz, int M, int C,
+                              const float *mean, const float *rstd, int relu, float *partial, float *dbeta, float *dgamma,
+                              t2h_stream_t stream) {
+    if (!gy || !z || !mean || !rstd || !partial || !dbeta || !dgamma || (relu && !y)) return fail(T2H_ERR_ARG, "bn_bwd_reduce: null pointer");
+    if (!bn_shape_ok(M, C) || ldg < C || ldz < C || (relu && ldy < C))
+        return fail(T2H_ERR_ARG, "bn_bwd_reduce: bad shape M=%d C=%d ldg=%d ldy=%d ldz=%d", M, C, ldg, ldy, ldz);
+    hipStream_t s = as_stream(stream);
+    const unsigned nslabs = blocks_for(M, kBnSlab);
+    hipLaunchKernelGGL(bn_partial_kernel<2>, dim3(nslabs, blocks_for(C, 64)), dim3(64, kBnWaves), 0, s, z, ldz, M, C, mean, rstd, gy, ldg,
+                       relu ? y : gy, relu ? ldy : ldg, relu ? 0u : 0xffffffffu, partial);      // (relu == 0: the mask is all ones)
+    hipLaunchKernelGGL(bn_finish_kernel, dim3(blocks_for(C, 256)), dim3(256), 0, s, partial, (int)nslabs, C, 2, 1.0f, 0.0f, dbeta, dgamma);
+    note_kernel("bn_partial_kernel");
+    return check_launch("bn_bwd_reduce");
+}
+
+T2H_API int t2h_bn_bwd_apply(const float *gy, int ldg, const float *y, int ldy, const float *z, int ldz, int M, int C,
+                             const float *mean, const float *rstd, const float *gamma, const float *dbeta, const float *dgamma,
+                             int relu, float *dz, int gld, t2h_stream_t stream) {
+    if (!gy || !z || !mean || !rstd || !gamma || !dbeta || !dgamma || !dz || (relu && !y))
+        return fail(T2H_ERR_ARG, "bn_bwd_apply: null pointer");
+    if (!bn_shape_ok(M, C) || ldg < C || ldz < C || (relu && ldy < C) || gld < C || gld > 64 * 65535)
+        return fail(T2H_ERR_ARG, "bn_bwd_apply: bad shape M=%d C=%d ldg=%d ldy=%d ldz=%d gld=%d", M, C, ldg, ldy, ldz, gld);
+    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(blocks_for(M, kBnSlab), blocks_for(gld, 64)), dim3(64, kBnWaves), 0, as_stream(stream),
+                       gy, ldg, relu ? y : gy, relu ? ldy : ldg, z, ldz, M, C, mean, rstd, gamma, dbeta, dgamma, (float)M,
+                       relu ? 0u : 0xffffffffu, dz, gld);
+    note_kernel("bn_bwd_apply_kernel");
+    return check_launch("bn_bwd_apply");
 }

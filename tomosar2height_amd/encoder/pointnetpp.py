@@ -1,5 +1,5 @@
-"""PointNetPlusPlus (reference: tomosar2height/encoder/pointnetpp.py:16-173) on the MI355X path: inference, and gradients of
-every parameter in ``eval()`` (fine-tuning with frozen BatchNorm statistics).
+"""PointNetPlusPlus (reference: tomosar2height/encoder/pointnetpp.py:16-173) on the MI355X path: inference, gradients of
+every parameter in ``eval()`` (fine-tuning with frozen BatchNorm statistics), and -- opt-in -- training with batch statistics.
 
 Constructor arguments, ``state_dict`` keys and shapes are the reference's (``sa{1,2,3}`` / ``fp{3,2,1}`` with ``mlp_convs.{k}`` and
 ``mlp_bns.{k}``, BatchNorm buffers and ``num_batches_tracked`` included, ``unet.*``), so a reference checkpoint loads with
@@ -8,7 +8,11 @@ runs on csrc/pnpp.hip (``pointops``); every 1 x 1 ``Conv2d`` / ``Conv1d`` + Batc
 the fp32 MFMA kernels (``mlp.linear_fwd_`` with ``relu_out``) with the BatchNorm running statistics folded into weight and
 bias; rasterisation and the ALTO / plain U-Net are the modules the default encoder uses.
 
-``eval()`` only.  ``forward`` under ``train()`` raises: BatchNorm batch statistics are not built (DESIGN.md sections 4.9 and 8).
+``eval()`` by default: ``forward`` under ``train()`` raises unless the encoder was built with ``batch_statistics=True`` (config:
+``model.encoder_kwargs``), the opt-in switch for BatchNorm batch statistics (DESIGN.md sections 4.9 and 8).  With it, a stage
+under ``train()`` runs ``_ChainBatchStats``: raw-weight products, the batch statistics of every layer's rows, their backward and
+the running-average updates on csrc/pnpp.hip (``t2h_bn_*``); the switch is a plain attribute (no ``state_dict`` entry) and has no
+effect in ``eval()``.
 In ``eval()`` with gradients enabled and an encoder parameter (or an incoming feature) that requires one, the stages build an
 autograd graph: the layers run on the same products forward (``_Chain``: ``linear_dgrad_`` / ``linear_wgrad_`` backward, the
 ReLU masks fused into the data gradients), the grouped max, the grouped rows and the 3-NN propagation have their adjoints in
@@ -51,6 +55,17 @@ class _FoldedLayers(nn.Module):
             self.mlp_bns.append(bn(out))
             last = out
         self.__dict__["_fold"] = _lib.Derived()
+        self.batch_statistics = False      # train(): BatchNorm batch statistics (``_ChainBatchStats``); a plain attribute, no state
+
+    def _refuse_training(self, name):
+        """``train()`` without the switch: the stage has no batch statistics to offer."""
+        if self.training and not self.batch_statistics:
+            raise NotImplementedError(f"{name} runs in eval() only: BatchNorm batch statistics are not built by default; "
+                                      f"construct PointNetPlusPlus(batch_statistics=True) (config: model.encoder_kwargs), or set "
+                                      f"``stage.batch_statistics = True``, to train with them")
+
+    def wants_batch_stats(self) -> bool:
+        return self.training and self.batch_statistics
 
     def folded(self):
         pairs = list(zip(self.mlp_convs, self.mlp_bns))
@@ -94,11 +109,14 @@ class _FoldedLayers(nn.Module):
     def _chain(self, rows, nsample=0, graph=False):
         """relu(bn(conv(.))) of every layer over [M, K] rows; ``nsample`` > 0: followed by the max over each group of
         ``nsample`` consecutive rows.  ``graph``: as one autograd node (``_Chain``)."""
-        if graph:
+        if graph or self.wants_batch_stats():
             widths = [conv.weight.shape[0] for conv in self.mlp_convs]
             if any(w % 4 for w in widths):
                 raise NotImplementedError(f"PointNetPlusPlus gradients need layer widths that are multiples of 4 (16-byte rows of "
                                           f"the data- and weight-gradient products), got {widths}; inference takes any width")
+        if self.wants_batch_stats():
+            return self._chain_batch_stats(rows, nsample)
+        if graph:
             return _Chain.apply(rows, nsample, *[t for wb in self.folded_graph() for t in wb])
         with torch.no_grad():
             for w, b in self.folded():
@@ -108,6 +126,76 @@ class _FoldedLayers(nn.Module):
             if nsample:
                 rows = pointops.group_max_rows(rows, nsample)
         return rows
+
+
+    def _chain_batch_stats(self, rows, nsample):
+        """The training-mode chain: per layer the raw weight (reshaped to [C, K], zero-padded to ``_pad4(K)`` columns: torch
+        operations under autograd, so ``dW`` reaches ``conv.weight`` through them), its bias, gamma and beta go into ONE node;
+        the running statistics are updated in place inside it, gradients enabled or not."""
+        args, bns = [], []
+        for conv, bn in zip(self.mlp_convs, self.mlp_bns):
+            _lib.require_device(conv.weight, what="PointNetPlusPlus layer")
+            if bn.momentum is None or not bn.track_running_stats or not bn.affine:
+                raise NotImplementedError("PointNetPlusPlus batch statistics: affine BatchNorm with running statistics and a fixed "
+                                          "momentum (the reference's layers) only")
+            w = conv.weight.reshape(conv.weight.shape[0], -1)
+            k = w.shape[1]
+            args += [torch.nn.functional.pad(w, (0, _pad4(k) - k)), conv.bias, bn.weight, bn.bias]
+            bns.append(bn)
+        return _ChainBatchStats.apply(rows, nsample, bns, *args)
+
+
+class _ChainBatchStats(torch.autograd.Function):
+    """The layers of a stage under ``train()`` with ``batch_statistics``: per layer z = x W^T + b (``linear_fwd_``, the raw
+    weight, no fold), the batch statistics of z's columns (``t2h_bn_col_stats``), y = relu(z * s + t) (``t2h_bn_apply_relu``) and
+    the momentum update of the layer's running statistics (``t2h_bn_running_update``, ``num_batches_tracked += 1``); then
+    (``nsample`` > 0) the max over each group of rows.  One node.  Backward, per layer from the last: the gradient of y comes from
+    ``t2h_group_max_bwd(relu=1)`` (set abstraction; the mask is then applied) or is the incoming one (the mask is applied by
+    ``t2h_bn_bwd_reduce`` / ``t2h_bn_bwd_apply`` with ``relu=1``, as for every inner layer); ``bwd_reduce`` gives dbeta and dgamma,
+    ``bwd_apply`` dz, ``linear_wgrad_`` dW and db, ``linear_dgrad_`` (no mask) the gradient of the layer's input."""
+
+    @staticmethod
+    def forward(ctx, rows, nsample, bns, *params):
+        n = len(bns)
+        xs, zs, ys, stats = [rows], [], [], []
+        for k, bn in enumerate(bns):
+            w, b, gamma, beta = params[4 * k:4 * k + 4]
+            c = w.shape[0]
+            z = torch.empty(xs[-1].shape[0], c, dtype=torch.float32, device=rows.device)
+            mlp.linear_fwd_(xs[-1], w, b, z, relu_out=False)
+            mean, var, rstd = pointops.bn_col_stats(z, c, bn.eps)
+            y = pointops.bn_apply_relu(z, c, mean, rstd, gamma, beta)
+            pointops.bn_running_update(mean, var, z.shape[0], bn.momentum, bn.running_mean, bn.running_var)
+            bn.num_batches_tracked.add_(1)
+            zs.append(z), ys.append(y), stats.extend((mean, rstd)), xs.append(y)
+        out = pointops._group_max_rows(ys[-1], nsample, ys[-1].shape[1]) if nsample else ys[-1]
+        ctx.nsample, ctx.layers = nsample, n
+        ctx.save_for_backward(*xs[:n], *zs, *ys, *stats, *params[0::4], *params[2::4], *((out,) if nsample else ()))
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        n = ctx.layers
+        sv = ctx.saved_tensors
+        xs, zs, ys, stats, ws, gammas = sv[:n], sv[n:2 * n], sv[2 * n:3 * n], sv[3 * n:5 * n], sv[5 * n:6 * n], sv[6 * n:7 * n]
+        g = gout.contiguous()
+        relu = True
+        if ctx.nsample:
+            g, relu = pointops.group_max_bwd(ys[n - 1], sv[-1], g, ctx.nsample, relu=True), False
+        grads = [None] * (4 * n)
+        for k in range(n - 1, -1, -1):
+            x, z, y, w, gamma, (mean, rstd) = xs[k], zs[k], ys[k], ws[k], gammas[k], stats[2 * k:2 * k + 2]
+            c = w.shape[0]
+            dbeta, dgamma = pointops.bn_bwd_reduce(g, y, z, c, mean, rstd, relu)
+            dz = pointops.bn_bwd_apply(g, y, z, c, mean, rstd, gamma, dbeta, dgamma, relu)
+            if ctx.needs_input_grad[3 + 4 * k] or ctx.needs_input_grad[4 + 4 * k]:
+                dw, db = torch.empty_like(w), torch.empty(c, dtype=torch.float32, device=w.device)
+                mlp.linear_wgrad_(dz, x, dw, db)
+                grads[4 * k], grads[4 * k + 1] = dw, db
+            grads[4 * k + 2], grads[4 * k + 3] = dgamma, dbeta
+            if k > 0 or ctx.needs_input_grad[0]:
+                g, relu = mlp.linear_dgrad_(dz, w, torch.empty_like(x), mask=None), True
+        return (g if ctx.needs_input_grad[0] else None, None, None, *grads)
 
 
 class _Chain(torch.autograd.Function):
@@ -151,6 +239,8 @@ class _Chain(torch.autograd.Function):
             if k > 0 or ctx.needs_input_grad[0]:
                 g = mlp.linear_dgrad_(g, w, torch.empty_like(x), mask=x if k > 0 else None)
         return (g if ctx.needs_input_grad[0] else None, None, *grads)
+
+
 class PointNetSetAbstraction(_FoldedLayers):
     def __init__(self, npoint, radius, nsample, in_channel, mlp, group_all):
         super().__init__()
@@ -160,8 +250,7 @@ class PointNetSetAbstraction(_FoldedLayers):
     def forward_rows(self, xyz, points, start=None, trace=None):
         """Point-major form of pointnetpp.py:31-57: ``xyz`` [B, N, 3], ``points`` [B, N, D] or None -> new_xyz [B, S, 3],
         new_points [B, S, D'].  ``trace``: a dict that receives ``fps_idx`` and the ball ``idx``."""
-        if self.training:
-            raise NotImplementedError("PointNetSetAbstraction runs in eval() only: BatchNorm batch statistics are not built")
+        self._refuse_training("PointNetSetAbstraction")
         pointops._cloud(xyz, "PointNetSetAbstraction xyz")
         b, n, _ = xyz.shape
         d = 0 if points is None else points.shape[2]
@@ -196,6 +285,24 @@ class PointNetSetAbstraction(_FoldedLayers):
         return new_xyz.permute(0, 2, 1), new_points.permute(0, 2, 1)
 
 
+class _RowConstant(torch.autograd.Function):
+    """Identity whose gradient is exactly zero: the one source row of a propagation over ONE cloud (``fp3`` at B = 1, the batch a
+    ``Trainer`` tile is).  The ``repeat`` branch copies it to every target, so in z = [points1 | row] W^T + b of the first layer
+    it is a per-channel constant over all M rows, which the batch statistics remove (z - mean): the output does not depend on
+    it, and its exact gradient -- and with it every gradient of ``sa3`` -- is 0.  The chain rule through the rounded kernels
+    would hand back rounding noise in its place (sum_r dz W, with sum_r dz = 0 only in exact arithmetic); this returns the
+    exact value, so ``sa3``'s parameters get zero gradients (not ``None``: weight decay still sees them).  With two or more
+    clouds the row is a constant per cloud only and the ordinary adjoint runs."""
+
+    @staticmethod
+    def forward(ctx, points2):
+        return points2.view_as(points2)
+
+    @staticmethod
+    def backward(ctx, g):
+        return torch.zeros_like(g)
+
+
 class PointNetFeaturePropagation(_FoldedLayers):
     def __init__(self, in_channel, mlp):
         super().__init__()
@@ -204,11 +311,12 @@ class PointNetFeaturePropagation(_FoldedLayers):
     def forward_rows(self, xyz1, xyz2, points1, points2, trace=None):
         """Point-major form of pointnetpp.py:70-109: targets ``xyz1`` [B, N, 3] (features ``points1`` [B, N, D1] or None), sources
         ``xyz2`` [B, S, 3] with ``points2`` [B, S, D2] -> [B, N, D'].  ``trace`` receives the 3-NN ``idx`` and ``weight``."""
-        if self.training:
-            raise NotImplementedError("PointNetFeaturePropagation runs in eval() only: BatchNorm batch statistics are not built")
+        self._refuse_training("PointNetFeaturePropagation")
         b, n, _ = xyz1.shape
         graph = self.wants_graph(points1, points2)
         with torch.set_grad_enabled(graph):
+            if graph and self.wants_batch_stats() and b == 1 and xyz2.shape[1] == 1 and points2.requires_grad:
+                points2 = _RowConstant.apply(points2)
             interp, idx, weight = pointops.three_nn_interpolate(xyz1, xyz2, points2)
             if trace is not None:
                 trace["idx"], trace["weight"], trace["interpolated"] = idx, weight, interp
@@ -226,7 +334,7 @@ class PointNetFeaturePropagation(_FoldedLayers):
 
 class PointNetPlusPlus(nn.Module):
     def __init__(self, feature_dim=128, dim=3, hidden_dim=None, scatter_type=None, unet_type="alto", unet_kwargs=None,
-                 plane_resolution=None):
+                 plane_resolution=None, batch_statistics: bool = False):
         super().__init__()
         self.sa1 = PointNetSetAbstraction(npoint=512, radius=0.2, nsample=32, in_channel=dim + 3, mlp=[64, 64, 128], group_all=False)
         self.sa2 = PointNetSetAbstraction(npoint=128, radius=0.4, nsample=64, in_channel=128 + 3, mlp=[128, 128, 256], group_all=False)
@@ -245,6 +353,9 @@ class PointNetPlusPlus(nn.Module):
         self.reso_plane = plane_resolution
         self.channels_last = False
         self.fps_start = None          # see the module docstring
+        self.batch_statistics = bool(batch_statistics)
+        for stage in (self.sa1, self.sa2, self.sa3, self.fp3, self.fp2, self.fp1):
+            stage.batch_statistics = self.batch_statistics
 
     def set_channels_last(self, flag: bool):
         """Keep the grid side in channels_last memory so planes need no NCHW<->NHWC copies."""
@@ -275,9 +386,10 @@ class PointNetPlusPlus(nn.Module):
 
     def forward(self, xyz: torch.Tensor, trace: dict = None) -> Dict[str, torch.Tensor]:
         """``xyz`` [B, N, dim] in [0, 1) -> ``{'xy': [B, feature_dim, R, R]}``."""
-        if self.training:
-            raise NotImplementedError("PointNetPlusPlus runs in eval() only: training needs BatchNorm batch statistics, which are "
-                                      "not built; gradients of every parameter are available in eval() (frozen statistics)")
+        if self.training and not self.batch_statistics:
+            raise NotImplementedError("PointNetPlusPlus runs in eval() only by default: training needs BatchNorm batch statistics, "
+                                      "which are opt-in -- PointNetPlusPlus(batch_statistics=True) (config: model.encoder_kwargs); "
+                                      "gradients of every parameter are also available in eval() (frozen statistics)")
         pointops._cloud(xyz, "PointNetPlusPlus", cols=None)
         xyz = xyz.contiguous()
         b, n, dim = xyz.shape

@@ -36,6 +36,11 @@ SIGNATURES = {
     "t2h_group_max_bwd": (_i, [_vp, _i, _i64, _i, _i, _vp, _vp, _i, _vp, _i, _vp]),
     "t2h_index_transpose": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "t2h_rows_gather_bwd": (_i, [_vp, _i, _i, _i, _vp, _i, _vp, _vp, _i, _i, _i, _vp, _vp]),
+    "t2h_bn_col_stats": (_i, [_vp, _i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
+    "t2h_bn_apply_relu": (_i, [_vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
+    "t2h_bn_running_update": (_i, [_vp, _vp, _i, _i, _f, _vp, _vp, _vp]),
+    "t2h_bn_bwd_reduce": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "t2h_bn_bwd_apply": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp]),
 }
 
 FPS_ONE_WG_MAX = 2048       # T2H_FPS_ONE_WG_MAX
@@ -43,6 +48,7 @@ FPS_ONE_WG_MAX = 2048       # T2H_FPS_ONE_WG_MAX
 # take the one-workgroup form and larger ones slices of FPS_SLICE_DEFAULT; set (a multiple of 64), EVERY cloud takes the sliced
 # form with that slice -- how a test runs it on a small cloud.  Both forms give the same bytes.
 FPS_SLICE_DEFAULT = 1024
+BN_SLAB = 256               # T2H_BN_SLAB: rows per slab of the BatchNorm column reductions
 
 _lib.declare("t2h_pnpp.h", SIGNATURES)
 load = _lib.load
@@ -309,3 +315,93 @@ def three_nn_interpolate(xyz1: torch.Tensor, xyz2: torch.Tensor, points2: torch.
     if torch.is_grad_enabled() and points2.requires_grad:
         return _ThreeNN.apply(points2, xyz1, xyz2)
     return _three_nn_interpolate(xyz1, xyz2, points2)
+
+
+# ------------------------------------------------------------------------------------------- BatchNorm batch statistics
+def _bn_rows(t, c, what):
+    """``t`` as fp32 device rows [M, >= c] with unit column stride (a column slice of wider rows stays a view)."""
+    _lib.require_device(t, what=what)
+    if t.dim() != 2 or t.dtype != torch.float32 or t.stride(1) != 1 or t.shape[1] < c or t.stride(0) < t.shape[1]:
+        raise ValueError(f"{what}: expected fp32 rows [M, >= {c}] with unit column stride, got {t.dtype} {tuple(t.shape)}")
+    return t
+
+
+def _bn_rows_count(m: int, c: int):
+    if m < 2:                                                  # torch's wording (torch.nn.functional._verify_batch_size)
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {torch.Size([m, c])}")
+
+
+def _bn_partial(m, c, planes, device):
+    return torch.empty(planes * (-(-m // BN_SLAB)) * c, dtype=torch.float32, device=device)
+
+
+def bn_col_stats(z: torch.Tensor, c: int, eps: float):
+    """(mean, var, rstd) [c] of the columns 0 .. c of the rows ``z`` [M, ld]: the biased batch variance by two passes and
+    ``rstd = 1 / sqrt(var + eps)`` (t2h_bn_col_stats; fixed association, include/t2h_pnpp.h)."""
+    _bn_rows(z, c, "bn_col_stats")
+    m = z.shape[0]
+    _bn_rows_count(m, c)
+    mean, var, rstd = (torch.empty(c, dtype=torch.float32, device=z.device) for _ in range(3))
+    partial = _bn_partial(m, c, 1, z.device)
+    _lib.call("t2h_bn_col_stats", _lib.ptr(z), z.stride(0), m, c, float(eps), _lib.ptr(partial), _lib.ptr(mean), _lib.ptr(var),
+              _lib.ptr(rstd), _lib.stream(), nbytes=8 * m * c, flops=4 * m * c)
+    return mean, var, rstd
+
+
+def bn_apply_relu(z: torch.Tensor, c: int, mean, rstd, gamma, beta, ldy: int = None) -> torch.Tensor:
+    """y [M, ldy] = relu(z * s + t), s = gamma * rstd, t = beta - mean * s; columns c .. ldy are zero (t2h_bn_apply_relu)."""
+    _bn_rows(z, c, "bn_apply_relu")
+    _lib.require_device(mean, rstd, gamma, beta, what="bn_apply_relu")
+    m = z.shape[0]
+    _bn_rows_count(m, c)
+    ldy = c if ldy is None else ldy
+    y = torch.empty(m, ldy, dtype=torch.float32, device=z.device)
+    _lib.call("t2h_bn_apply_relu", _lib.ptr(z), z.stride(0), m, c, _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(gamma), _lib.ptr(beta),
+              _lib.ptr(y), ldy, _lib.stream(), nbytes=4 * m * (c + ldy), flops=3 * m * c)
+    return y
+
+
+def bn_running_update(mean, var, m: int, momentum: float, running_mean, running_var):
+    """The momentum recurrence of ``running_mean`` / ``running_var`` in place, with the unbiased variance
+    (t2h_bn_running_update)."""
+    _lib.require_device(mean, var, running_mean, running_var, what="bn_running_update")
+    c = mean.numel()
+    _bn_rows_count(m, c)
+    if not (running_mean.is_contiguous() and running_var.is_contiguous() and running_mean.numel() == c == running_var.numel()
+            and running_mean.dtype == running_var.dtype == torch.float32):
+        raise ValueError("bn_running_update: contiguous fp32 running statistics of the statistics' length expected")
+    _lib.call("t2h_bn_running_update", _lib.ptr(mean), _lib.ptr(var), m, c, float(momentum), _lib.ptr(running_mean),
+              _lib.ptr(running_var), _lib.stream(), nbytes=24 * c)
+    # written behind torch's back: whatever is keyed on their version counters (the eval() fold) is stale
+    torch.autograd.graph.increment_version((running_mean, running_var))
+    return running_mean, running_var
+
+
+def bn_bwd_reduce(gy, y, z, c: int, mean, rstd, relu: bool):
+    """(dbeta, dgamma) [c]: the column sums of g and g * xhat, g = ``gy`` masked by ``y > 0`` when ``relu`` (t2h_bn_bwd_reduce)."""
+    _bn_rows(gy, c, "bn_bwd_reduce gy"), _bn_rows(z, c, "bn_bwd_reduce z")
+    if relu:
+        _bn_rows(y, c, "bn_bwd_reduce y")
+    m = z.shape[0]
+    _bn_rows_count(m, c)
+    dbeta, dgamma = (torch.empty(c, dtype=torch.float32, device=z.device) for _ in range(2))
+    partial = _bn_partial(m, c, 2, z.device)
+    _lib.call("t2h_bn_bwd_reduce", _lib.ptr(gy), gy.stride(0), _lib.ptr(y) if relu else None, y.stride(0) if relu else 0, _lib.ptr(z),
+              z.stride(0), m, c, _lib.ptr(mean), _lib.ptr(rstd), int(bool(relu)), _lib.ptr(partial), _lib.ptr(dbeta), _lib.ptr(dgamma),
+              _lib.stream(), nbytes=4 * m * c * (3 if relu else 2), flops=5 * m * c)
+    return dbeta, dgamma
+
+
+def bn_bwd_apply(gy, y, z, c: int, mean, rstd, gamma, dbeta, dgamma, relu: bool, gld: int = None) -> torch.Tensor:
+    """dz [M, gld] = gamma * rstd * (g - dbeta / M - xhat * dgamma / M); columns c .. gld are zero (t2h_bn_bwd_apply)."""
+    _bn_rows(gy, c, "bn_bwd_apply gy"), _bn_rows(z, c, "bn_bwd_apply z")
+    if relu:
+        _bn_rows(y, c, "bn_bwd_apply y")
+    m = z.shape[0]
+    _bn_rows_count(m, c)
+    gld = c if gld is None else gld
+    dz = torch.empty(m, gld, dtype=torch.float32, device=z.device)
+    _lib.call("t2h_bn_bwd_apply", _lib.ptr(gy), gy.stride(0), _lib.ptr(y) if relu else None, y.stride(0) if relu else 0, _lib.ptr(z),
+              z.stride(0), m, c, _lib.ptr(mean), _lib.ptr(rstd), _lib.ptr(gamma), _lib.ptr(dbeta), _lib.ptr(dgamma), int(bool(relu)),
+              _lib.ptr(dz), gld, _lib.stream(), nbytes=4 * m * (c * (3 if relu else 2) + gld), flops=6 * m * c)
+    return dz

@@ -161,6 +161,14 @@ class Trainer:
         finally:
             self._unet.compose_cache = prev
 
+    # ------------------------------------------------------------------------------------------ per-tile statistics
+    def _per_tile_statistics(self) -> bool:
+        """True for a model whose point encoder normalises with BATCH statistics (``PointNetPlusPlus(batch_statistics=True)``).
+        The reference's statistics are per tile (batch = 1), so such a model's tiles are issued one by one -- no coalescing, no
+        micro-batch: the statistics would mix tiles -- and on one stream: every forward updates the running statistics, and
+        consecutive updates must stay in order (no two-stream tile pipeline, no captured graph)."""
+        return bool(getattr(getattr(self.model, "point_encoder", None), "batch_statistics", False))
+
     # ------------------------------------------------------------------------------------------ loss
     def _losses(self, data, mask_threshold):
         device = self.device
@@ -204,6 +212,8 @@ class Trainer:
         gradient bucket, i.e. at least one eager ``train_step`` first.  In channels_last mode the replay is bit-identical to
         eager execution (with the NCHW / MIOpen grid side: up to MIOpen's run-to-run conv-wgrad rounding).  At N = 131072
         the step is GPU-bound (measured: no gain); it pays for small tiles."""
+        if self._per_tile_statistics():
+            raise NotImplementedError("capture_graph: not built for a point encoder with BatchNorm batch statistics")
         if self.bucket is None:
             raise RuntimeError("capture_graph: run one eager train_step first (the gradient bucket must exist)")
         self.flush_pipeline()
@@ -244,6 +254,9 @@ class Trainer:
         pipeline (6.7 ms per tile) no longer depends on how fast the host issues.  Tiles of other shapes (real tiles have
         varying N) run eagerly.  Needs the gradient bucket, i.e. at least one eager ``train_step`` first; the weight gradients
         stay on the tile's stream inside the graphs (graph branches measured slower than a linear graph on this stack)."""
+        if self._per_tile_statistics():
+            raise NotImplementedError("capture_pipeline_graphs: not built for a point encoder with BatchNorm batch statistics "
+                                      "(its tiles run on one stream)")
         if self.bucket is None:
             raise RuntimeError("capture_pipeline_graphs: run one eager train_step first (the gradient bucket must exist)")
         self._snapshots_off()
@@ -343,6 +356,8 @@ class Trainer:
     def _coalescible(self, data) -> bool:
         """Raw device tensors only: a cloud [1, N, 3] (+ image) + target, as the reference's loader hands them over.  A tile whose
         index was built ahead (``prepare``) is issued on its own -- its index is per tile."""
+        if self._per_tile_statistics():
+            return False
         cloud = data.get("inputs") if self.use_cloud else None
         if self.use_cloud and not (torch.is_tensor(cloud) and cloud.dim() == 3 and cloud.shape[0] == 1):
             return False
@@ -373,8 +388,12 @@ class Trainer:
                              f"({self.accumulated_steps} of {self.local_every} tiles accumulated)")
         if n_tiles == 1 and isinstance(data, (list, tuple)):
             data = data[0]
+        per_tile = self._per_tile_statistics()
+        if per_tile and n_tiles > 1:
+            raise ValueError(f"a micro-batch of {n_tiles} tiles would mix the tiles in the point encoder's BatchNorm batch statistics "
+                             f"(the reference's are per tile): hand the tiles to train_step one by one")
         first = data[0] if n_tiles > 1 else data
-        if (self.pipeline_tiles and (n_tiles == 1 or self.pipeline_micro_batches) and self.bucket is not None and self._graph is None
+        if (not per_tile and self.pipeline_tiles and (n_tiles == 1 or self.pipeline_micro_batches) and self.bucket is not None and self._graph is None
                 and isinstance(first, dict) and torch.is_tensor(first.get("dsm")) and next(self.model.parameters()).is_cuda):
             return self._train_step_pipelined(data, n_tiles)
         self.flush_pipeline()
