@@ -9,27 +9,44 @@
 
 What a buffer holds when it is handed out:
 
-=========  ==========================  ===================================  ====================================
-``fill``   raw workspace               typed floating tensor                typed integer / bool tensor
-=========  ==========================  ===================================  ====================================
-"nan"      0xFF bytes                  0xFF bytes (NaN in f16/bf16/f32/f64)  stale from ``record``, else zero
-"stale"    the recorded run's buffer   0xFF bytes                           stale from ``record`` (required)
-"zero"     zero                        zero                                 zero
-"record"   zero                        0xFF bytes                           zero
-=========  ==========================  ===================================  ====================================
+=========  ==========================  =====================  ===================================  ====================================
+``fill``   raw workspace               ... at an integer site  typed floating tensor                typed integer / bool tensor
+=========  ==========================  =====================  ===================================  ====================================
+"nan"      0xFF bytes                  recorded, else zero    0xFF bytes (NaN in f16/bf16/f32/f64)  stale from ``record``, else zero
+"stale"    the recorded run's buffer   recorded               0xFF bytes                           stale from ``record`` (required)
+"zero"     zero                        recorded, else zero    zero                                 zero
+"record"   zero                        zero                   0xFF bytes                           zero
+=========  ==========================  =====================  ===================================  ====================================
 
 "record" is the fill of the run whose ``.log`` a stale run replays: its raw workspaces start from zero, so a slot that neither
 run writes holds zero in the replay, never 0xFF.  ``nan_sites``: under "stale", a raw workspace whose call site contains one of
 these strings (``"ops.py:222"``) holds floating data only and gets a fresh 0xFF buffer instead of the recorded one.
 
 Integer tensors, and raw workspaces that hold integers, never get 0xFF: a kernel that used an unwritten one as an index would turn a latent bug into a wild address.
+``int_sites`` is the mirror of ``nan_sites`` for that rule: a raw workspace whose call site matches one of them holds the recorded
+run's bytes whenever a ``record`` is being replayed and zero otherwise, under EVERY fill, and whatever ``nan_sites`` says.  The
+default, ``INT_SITES``, names the tile builds (``TileIndex.__init__`` / ``_init_ragged`` in tile.py: sort keys, histograms, scans).
 A stale value is what the SAME call sequence left there on another input of the same shape, so it is in range for the shape.
 ``record=`` takes the ``.log`` of an earlier ``guarded_scratch`` block; the allocation sequence (kind and byte count) of the
 replaying block must equal the recorded one -- any difference raises ``ScratchGuardError``, there is no fall-back.
 
+A site is a substring of ``"<file>:<line> (<function>)"``, or a tuple of substrings that must all occur.
+
+Workspaces that outlive the block (``fresh_sites``, default ``FRESH_SITES``: the split-weight buffers of grid.py's
+``SplitWeightCache._get``, which live as long as their weight and are updated in place).  The view keeps its banded allocation
+alive and the bands are checked when the block exits, so outliving it is harmless.  But under "stale" the recorded run's buffer
+itself may still be some live weight's cache entry, and handing it out again would alias two entries.  The choice made here: such
+a site gets a FRESH banded buffer holding a COPY of the recorded bytes (the recording model need not be dropped first).  The
+allocation-sequence check (kind, byte count) holds for these sites like for any other.  They hold packed 16-bit planes and a
+trailer of scale and exponent, never an index, so under "nan" (or as a ``nan_sites`` member) they take 0xFF.
+
 On exit: ``torch.cuda.synchronize()`` (side streams are in use), then every guard band is compared byte for byte; a damaged
 one raises ``ScratchGuardError`` naming the call site of the allocation.  Every buffer is kept alive until then.
 Not for use under hipGraph capture.
+
+Does NOT catch: a READ outside a buffer; a race that is usually won; anything under capture; an overrun of a typed tensor (an
+output, an index list kept by its caller) -- only ``_lib.workspace`` buffers are banded, which since the tile builds and the
+split-weight cache allocate through it is every raw byte buffer of the package (test_scratch_guard_cpu.py reads the sources).
 """
 import sys
 
@@ -41,6 +58,8 @@ FILLS = ("nan", "stale", "zero", "record")
 _TORCH_FUNCS = ("empty", "empty_like", "empty_strided")
 _THIS = __file__.rsplit(".", 1)[0]
 _REAL_EMPTY = torch.empty            # (the builtin, taken before any block patches it)
+INT_SITES = ("/tile.py:",)           # raw workspaces of integers: TileIndex.__init__ / _init_ragged (the only two of that file)
+FRESH_SITES = (("/grid.py:", "(_get)"),)     # SplitWeightCache._get: the buffer lives on in the cache
 
 
 class ScratchGuardError(AssertionError):
@@ -59,8 +78,13 @@ def _call_site():
     return "<unknown>" if f is None else f"{f.f_code.co_filename}:{f.f_lineno} ({f.f_code.co_name})"
 
 
+def _hit(site, keys):
+    return any(all(p in site for p in ((k,) if isinstance(k, str) else k)) for k in keys)
+
+
 class guarded_scratch:
-    def __init__(self, fill="nan", device_types=("cuda",), record=None, guard=GUARD, nan_sites=()):
+    def __init__(self, fill="nan", device_types=("cuda",), record=None, guard=GUARD, nan_sites=(), int_sites=INT_SITES,
+                 fresh_sites=FRESH_SITES):
         if fill not in FILLS:
             raise ValueError(f"fill must be one of {FILLS}")
         if fill == "stale" and record is None:
@@ -68,7 +92,7 @@ class guarded_scratch:
         if guard < GUARD:
             raise ValueError(f"guard bands are at least {GUARD} bytes")
         self.fill, self.device_types, self.record, self.guard = fill, tuple(device_types), record, guard
-        self.nan_sites = tuple(nan_sites)
+        self.nan_sites, self.int_sites, self.fresh_sites = tuple(nan_sites), tuple(int_sites), tuple(fresh_sites)
         self.log = []              # ("ws" | "typed", nbytes, tensor, ...) in allocation order; holds every buffer alive
         self._next = 0
         self._saved = None
@@ -92,14 +116,18 @@ class guarded_scratch:
             return self._real["workspace"](nbytes, device)
         site = _call_site()
         rec = self._recorded("ws", n, site)
-        if rec is not None and self.fill == "stale" and not any(k in site for k in self.nan_sites):
+        integer = _hit(site, self.int_sites)
+        replay = rec is not None and (integer or (self.fill == "stale" and not _hit(site, self.nan_sites)))
+        if replay and not _hit(site, self.fresh_sites):
             entry = ("ws", n) + rec[2:5] + (site,)             # the same buffer again, unmodified; its guards are checked again
         else:
             buf = self._real["empty"](n + 2 * self.guard + ALIGN, dtype=torch.uint8, device=device)
             off = self.guard + (-(buf.data_ptr() + self.guard)) % ALIGN
             buf.fill_(0xFF)
             view = buf[off:off + n]
-            if self.fill in ("zero", "record"):
+            if replay:
+                view.copy_(rec[2])                             # (a buffer that outlives the block: a copy of the recorded bytes)
+            elif integer or self.fill in ("zero", "record"):
                 view.zero_()
             entry = ("ws", n, view, buf, off, site)
         self.log.append(entry)

@@ -191,3 +191,110 @@ def test_tabled_signs_of_the_size_queries_hold():
         for name, args, sign in case.queries:
             size = int(_lib._entry(name)(*args))
             assert (size > 0) == (sign == ">0"), (case.id, name, args, size)
+
+
+def _standin(filename, name="build"):
+    """A function that asks for a raw workspace like a wrapper of the package, compiled under another file name: the harness knows
+    a call site by the file and function of the caller's frame.  ``overrun``: bytes written past the end (a host tensor write)."""
+    src = (f"def {name}(nbytes, overrun=0):\n"
+           "    from tomosar2height_amd import _lib\n"
+           "    ws = _lib.workspace(nbytes, 'cpu')\n"
+           "    if overrun:\n"
+           "        base = ws._base if ws._base is not None else ws\n"
+           "        start = ws.storage_offset() + ws.numel()\n"
+           "        base[start:start + overrun] = 0\n"
+           "    return ws\n")
+    scope = {}
+    exec(compile(src, filename, "exec"), scope)
+    return scope[name]
+
+
+def test_integer_sites_never_start_from_0xff():
+    """A raw workspace asked for from tile.py (the tile builds: sort keys, histograms) is zero under "nan", the recorded run's
+    bytes whenever a record is replayed -- also where ``nan_sites`` would make it NaN --, and banded like any other."""
+    build = _standin("/somewhere/tomosar2height_amd/tile.py")
+    other = _standin("/somewhere/tomosar2height_amd/ops.py")
+    with guarded_scratch("nan", CPU) as g:
+        ws, plain = build(48), other(48)
+        assert bool((ws == 0).all()) and bool((plain == 0xFF).all())
+    for _, n, view, buf, off, site in g.log:
+        assert "tile.py" in site or "ops.py" in site
+        assert view.data_ptr() % 512 == 0 and off >= GUARD and buf.numel() - off - n >= GUARD
+        assert bool((buf[:off] == 0xFF).all()) and bool((buf[off + n:] == 0xFF).all())
+    with guarded_scratch("record", CPU) as a:
+        ws = build(48)
+        assert bool((ws == 0).all())
+        ws[:5] = torch.arange(1, 6, dtype=torch.uint8)
+    for fill, kw in (("stale", {}), ("stale", {"nan_sites": ("tile.py",)}), ("nan", {}), ("zero", {})):
+        with guarded_scratch(fill, CPU, record=a.log, **kw) as g:
+            again = build(48)
+            assert again.tolist() == [1, 2, 3, 4, 5] + [0] * 43, (fill, kw)
+        assert g.damaged() == []
+    with guarded_scratch("nan", CPU, int_sites=()):                  # (the default set is what makes it an integer site)
+        assert bool((build(48) == 0xFF).all())
+    with pytest.raises(ScratchGuardError) as e:
+        with guarded_scratch("nan", CPU):
+            build(48, overrun=1)
+    msg = str(e.value)
+    assert "tile.py" in msg and "(build)" in msg and "48-byte workspace" in msg and "byte +48" in msg
+    with pytest.raises(ScratchGuardError, match="stale replay"):      # the sequence check holds for these sites too
+        with guarded_scratch("nan", CPU, record=a.log):
+            build(52)
+
+
+def test_a_workspace_that_outlives_the_block_is_a_fresh_copy_in_the_stale_replay():
+    """grid.py's ``SplitWeightCache._get`` keeps its buffer for the weight's lifetime: replaying hands out a NEW banded buffer
+    with a copy of the recorded bytes (never the recorded buffer, which may be a live cache entry); 0xFF under "nan"."""
+    get = _standin("/somewhere/tomosar2height_amd/grid.py", "_get")
+    elsewhere = _standin("/somewhere/tomosar2height_amd/grid.py", "conv3x3_fwd_")
+    with guarded_scratch("record", CPU) as a:
+        kept, scratch = get(32), elsewhere(32)
+        kept[:3] = 9
+        scratch[:3] = 4
+    with guarded_scratch("stale", CPU, record=a.log) as g:
+        mine, again = get(32), elsewhere(32)
+        assert mine.tolist() == [9] * 3 + [0] * 29 and mine.data_ptr() != kept.data_ptr()
+        assert again.data_ptr() == scratch.data_ptr()
+        mine[:] = 1                                                  # the cache updates in place: the recorded bytes stay
+    assert kept.tolist() == [9] * 3 + [0] * 29 and g.damaged() == []
+    entry = g.log[0]
+    assert bool((entry[3][:entry[4]] == 0xFF).all()) and bool((entry[3][entry[4] + 32:] == 0xFF).all())
+    with guarded_scratch("nan", CPU, record=a.log):
+        assert bool((get(32) == 0xFF).all()) and bool((elsewhere(32) == 0xFF).all())
+    with pytest.raises(ScratchGuardError, match="stale replay"):
+        with guarded_scratch("stale", CPU, record=a.log):
+            get(36)
+    with pytest.raises(ScratchGuardError) as e:
+        with guarded_scratch("stale", CPU, record=a.log):
+            get(32, overrun=2), elsewhere(32)
+    assert "grid.py" in str(e.value) and "(_get)" in str(e.value) and "byte +32" in str(e.value)
+
+
+# device uint8 buffers of the package that are NOT scratch: typed results the caller keeps.  (file, a substring of the allocation)
+_UINT8_RESULTS = (
+    ("ops.py", "t2h_pool_winner_stride"),       # the max-pool's winner bytes per row: saved for the backward
+    ("grid.py", "which = torch.empty("),        # the 2 x 2 max-pool's arg-max plane: saved for the backward
+    ("evaluator.py", "out = torch.empty(t.shape"),   # a predicate's 0 / 1 plane: the mask the evaluator keeps
+)
+
+
+def test_every_uint8_device_buffer_of_the_package_is_a_lib_workspace():
+    """Raw byte scratch comes from ``_lib.workspace`` alone (what scratch_guard.py bands): no other ``torch.empty`` / ``new_empty``
+    of ``torch.uint8`` in the package's Python text, but for the typed results listed above."""
+    hits = []
+    for path in sorted(glob.glob(os.path.join(ROOT, "tomosar2height_amd", "**", "*.py"), recursive=True)):
+        with open(path) as f:
+            text = f.read()
+        for m in re.finditer(r"(?:torch\.empty|\.new_empty)\(", text):
+            depth, end = 1, m.end()
+            while depth and end < len(text):                        # the whole call, to its closing parenthesis
+                depth += {"(": 1, ")": -1}.get(text[end], 0)
+                end += 1
+            call = text[text.rfind("\n", 0, m.start()) + 1:end]
+            if "uint8" in call:
+                hits.append((os.path.relpath(path, os.path.join(ROOT, "tomosar2height_amd")), " ".join(call.split())))
+    assert ("_lib.py", "return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)") in hits   # the search finds it
+    rest = [h for h in hits if h[0] != "_lib.py" and not any(h[0] == f and key in h[1] for f, key in _UINT8_RESULTS)]
+    assert not rest, f"uint8 buffers allocated by hand (use _lib.workspace, or list a typed result): {rest}"
+    unused = [a for a in _UINT8_RESULTS if not any(h[0] == a[0] and a[1] in h[1] for h in hits)]
+    assert not unused, f"allow-list entries that match nothing: {unused}"

@@ -14,6 +14,10 @@ Fill rule: "nan" only where reading the source shows the workspace holds floatin
 used as an index, offset, count or loop bound -- the ``why`` column gives the line the choice rests on.  No row is in the
 atomic mode: no package-level call of this table reaches ``t2h_sample_bwd_atomic`` (ops._sample_bwd takes the gather, the
 per-cell partials or the transposed matrix).
+
+``_sizing_cases``: the tile builds' workspaces and the split-weight buffers (both ``_lib.workspace``s, so banded) at the smallest
+shapes where their size queries can be wrong, each against the reference the suite already uses for the operation; the batched
+refresh of 25 split buffers has a test of its own at the end.
 """
 import numpy as np
 import pytest
@@ -21,7 +25,7 @@ import torch
 import torch.nn.functional as F
 
 from detinit import det_init_, synth_cloud
-from scratch_guard import guarded_scratch
+from scratch_guard import _hit, guarded_scratch
 
 pytestmark = pytest.mark.gpu
 D = torch.float64
@@ -187,7 +191,7 @@ def _conv_case(b, h, w, cin, cout, precision, fwd, dgrad, wgrad, weights=None):
         q.append((weights, (cin, cout), ">0"))
     return Case(f"conv3x3-{precision}-{'x'.join(map(str, s))}", "grid.conv3x3_fwd_ / conv3x3_dgrad_ / conv3x3_wgrad_", run, "nan",
                 "split-reduction slabs of float partial sums only (conv.hip:547-600, conv_bx3.hip:1137-1240); the split-weight "
-                "buffer (grid.py:227) is a uint8 tensor of packed 16-bit planes, never an index", q, check,
+                "buffer (grid.py:227) is a raw workspace of packed 16-bit planes, never an index", q, check,
                 {"grid.CONV_PRECISION": precision, "grid.BX3_MIN_PIXELS": 0, "grid.BX3_WGRAD": True})
 
 
@@ -603,6 +607,189 @@ def _model(train):
     return run, check
 
 
+# ------------------------------------------------------------------------------------------------ tile builds (tile.py)
+def _index_ref(cloud, reso):
+    """The index restatement of test_hip_ops.py::test_tile_index_bit_exact (the C oracle's cell of each point, Morton code, a
+    STABLE sort per tile, CSR offsets), as the four arrays the build writes -- so that they compare byte for byte."""
+    from oracle import c_oracle
+    from test_hip_ops import _morton
+    b, n, _ = cloud.shape
+    idx = c_oracle.coordinate2index(cloud.numpy(), reso)[:, 0]
+    m0 = reso * reso
+    code = _morton(idx % reso, idx // reso).astype(np.int64) + np.arange(b)[:, None] * m0
+    perm = np.stack([np.argsort(code[k], kind="stable") for k in range(b)])
+    counts = np.bincount(code.reshape(-1), minlength=b * m0)
+    return {"pts": np.concatenate([cloud.numpy()[k][perm[k]] for k in range(b)]),
+            "perm": perm.reshape(-1).astype(np.int32), "cell": np.take_along_axis(code, perm, 1).reshape(-1).astype(np.int32),
+            "off0": np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)}
+
+
+def _tile_case(b, n, reso):
+    def run(seed):
+        from tomosar2height_amd.tile import TileIndex
+        t = TileIndex(synth_cloud(n, seed=seed, batch=b).to(_dev()), reso)
+        assert t.out_of_domain() == 0
+        return {"pts": t.pts, "perm": t.perm, "cell": t.cell, "off0": t.off0}
+
+    def check(o, seed):
+        want = _index_ref(synth_cloud(n, seed=seed, batch=b), reso)
+        for k, ref in want.items():
+            got = o[k].cpu().numpy()
+            assert got.dtype == ref.dtype and got.shape == ref.shape and got.tobytes() == ref.tobytes(), k
+    return Case(f"tile-build-b{b}-n{n}-r{reso}", "TileIndex(cloud, R) (t2h_tile_build)", run, "stale",
+                "sort keys, histograms and scans (tile_index.hip); an integer site of the harness under every fill",
+                [("t2h_tile_workspace_bytes", (b, n, reso.bit_length() - 1), ">0")], check, sites=("/tile.py:",))
+
+
+def _ragged_tile_case(counts, reso):
+    def clouds(seed):
+        return [synth_cloud(k, seed=seed + 31 * i).to(_dev()) for i, k in enumerate(counts)]
+
+    def run(seed):
+        from tomosar2height_amd.tile import TileIndex
+        t = TileIndex(clouds(seed), reso)
+        assert t.ragged and t.n_points == sum(counts) and t.out_of_domain() == 0
+        return {"pts": t.pts, "perm": t.perm, "cell": t.cell, "off0": t.off0}
+
+    def check(o, seed):
+        """test_hip_ragged.py::test_ragged_tile_index_equals_the_single_tile_indices: tile by tile the single-tile index."""
+        from tomosar2height_amd.tile import TileIndex
+        m0, row = reso * reso, 0
+        assert o["pts"].shape == (sum(counts), 4) and o["off0"].numel() == len(counts) * m0 + 1
+        for b, (c, n) in enumerate(zip(clouds(seed), counts)):
+            one = TileIndex(c, reso)
+            assert torch.equal(o["pts"][row:row + n, :3], one.pts)
+            assert torch.equal(o["pts"][row:row + n, 3].view(torch.int32), torch.full((n,), b, dtype=torch.int32, device=_dev()))
+            assert torch.equal(o["perm"][row:row + n], one.perm)
+            assert torch.equal(o["cell"][row:row + n], one.cell + b * m0)
+            assert torch.equal(o["off0"][b * m0:(b + 1) * m0 + 1], one.off0 + row)
+            row += n
+    return Case(f"tile-build-ragged-{'+'.join(map(str, counts))}-r{reso}", "TileIndex([clouds], R) (t2h_tile_build_ragged)", run,
+                "stale", "as the uniform build; sized by (B, total, max count)",
+                [("t2h_tile_ragged_workspace_bytes", (len(counts), sum(counts), max(counts), reso.bit_length() - 1), ">0")], check,
+                sites=("/tile.py:",))
+
+
+# ------------------------------------------------------------------------------------------------ split-weight buffers (grid.py)
+_SPLIT_SITE = ("/grid.py:", "(_get)")                    # SplitWeightCache._get
+_SPLIT_QUERY = {("conv", "f16x2"): "t2h_conv3x3_f16x2_weights_bytes", ("conv", "bf16x3"): "t2h_conv3x3_bx3_weights_bytes",
+                ("gemm", "f16x2"): "t2h_gemm_f16x2_weights_bytes", ("gemm", "bf16x3"): "t2h_gemm_bx3_weights_bytes"}
+_SPLIT_WHY = ("packed 16-bit planes and a trailer of scale and exponent, never an index: may start from 0xFF; every byte of the "
+              "buffer is compared as well (the single prepare writes all of it, conv_bx3.hip:1447-1487)")
+
+
+def _split_conv_case(cin, cout, precision):
+    """Both 3x3 kinds at the smallest plane the split kernels take (4 x 32): ``get(w, False)`` under the forward, ``get(w, True)``
+    under the data gradient; float64 F.conv2d at test_hip_conv.py's 2e-5 of the max-norm."""
+    b, h, w = 1, 4, 32
+
+    def data(seed):
+        g = _gen(seed)
+        return (torch.randn(b, cin, h, w, generator=g), torch.randn(cout, cin, 3, 3, generator=g) * 0.1, torch.randn(cout, generator=g),
+                torch.randn(b, cout, h, w, generator=g))
+
+    def run(seed):
+        from tomosar2height_amd import grid
+        x, wt, bias, gy = data(seed)
+        assert grid.bx3_applicable(b, h, w, cin, cout)
+        wd = _cl(wt)
+        y = grid.conv3x3_fwd_(_cl(x), wd, bias.to(_dev()), grid._empty_cl(b, cout, h, w, _dev()))
+        dx = grid.conv3x3_dgrad_(_cl(gy), wd, grid._empty_cl(b, cin, h, w, _dev()))
+        return {"y": y, "dx": dx, "wf": grid.split_weights.get(wd, False).clone(), "wf_t": grid.split_weights.get(wd, True).clone()}
+
+    def check(o, seed):
+        x, wt, bias, gy = (t.double() for t in data(seed))
+        x.requires_grad_(True)
+        want = F.conv2d(x, wt, bias, padding=1)
+        want.backward(gy)
+        _close(o["y"], want, 2e-5, "y")
+        _close(o["dx"], x.grad, 2e-5, "dx")
+    return Case(f"split-conv3x3-{precision}-cin{cin}-cout{cout}", "SplitWeightCache.get, both orientations, under conv3x3_fwd_ / "
+                "conv3x3_dgrad_", run, "nan", _SPLIT_WHY, [(_SPLIT_QUERY["conv", precision], (cin, cout), ">0")], check,
+                {"grid.CONV_PRECISION": precision, "grid.BX3_MIN_PIXELS": 0}, sites=(_SPLIT_SITE,))
+
+
+def _split_gemm_case(k, n, precision, pad=0):
+    """Both matrix kinds at the fewest rows the split product takes (128): ``get_gemm(w [N,K], False)`` under y = x w^T + bias and
+    ``get_gemm(w [K,N], True)`` under y = x w; ``pad``: each weight is a column slice of a matrix ``pad`` columns wider (ldw > row
+    length).  float64 at test_hip_gemm.py's 2e-5 of the max-norm (test_gemm_bx3_rows_vs_float64)."""
+    m = 128
+
+    def data(seed):
+        g = _gen(seed)
+        return (torch.randn(m, k, generator=g), torch.randn(n, k + pad, generator=g) / k ** 0.5, torch.randn(k, n + pad, generator=g) / k ** 0.5,
+                torch.randn(n, generator=g))
+
+    def run(seed):
+        from tomosar2height_amd import _lib, grid, mlp
+        assert _lib.ws_bytes("t2h_gemm_bx3_supported", m, k, n)
+        x, wide_nk, wide_kn, bias = (t.to(_dev()) for t in data(seed))
+        w_nk, w_kn = wide_nk[:, pad // 2:pad // 2 + k], wide_kn[:, pad // 2:pad // 2 + n]
+        assert (w_nk.stride(0) > k) == (pad > 0) and (w_kn.stride(0) > n) == (pad > 0)
+        y_nk = mlp._gemm_bx3(x, w_nk, False, bias, None, torch.empty(m, n, device=_dev()), False, False, "split-gemm-nk")
+        y_kn = mlp._gemm_bx3(x, w_kn, True, None, None, torch.empty(m, n, device=_dev()), False, False, "split-gemm-kn")
+        return {"y_nk": y_nk, "y_kn": y_kn, "wf_nk": grid.split_weights.get_gemm(w_nk, False).clone(),
+                "wf_kn": grid.split_weights.get_gemm(w_kn, True).clone()}
+
+    def check(o, seed):
+        x, wide_nk, wide_kn, bias = (t.double() for t in data(seed))
+        _close(o["y_nk"], x @ wide_nk[:, pad // 2:pad // 2 + k].t() + bias, 2e-5, "y_nk")
+        _close(o["y_kn"], x @ wide_kn[:, pad // 2:pad // 2 + n], 2e-5, "y_kn")
+    return Case(f"split-gemm-{precision}-k{k}-n{n}" + (f"-ldw+{pad}" if pad else ""), "SplitWeightCache.get_gemm, [N,K] and [K,N], "
+                "under t2h_gemm_bx3 (mlp._gemm_bx3)", run, "nan", _SPLIT_WHY, [(_SPLIT_QUERY["gemm", precision], (k, n), ">0")],
+                check, {"grid.CONV_PRECISION": precision}, sites=(_SPLIT_SITE, "mlp.py:94"))
+
+
+def _split_up_case(cin, cout, precision):
+    """Both transposed-convolution kinds at the smallest plane the split kernels take (4 x 32 = 128 pixels): ``get_up(w, True)`` under
+    the forward, ``get_up(w, False)`` under the data gradient; float64 conv_transpose2d at test_hip_conv.py's 2e-5."""
+    b, h, w = 1, 4, 32
+
+    def data(seed):
+        g = _gen(seed)
+        return (torch.randn(b, cin, h, w, generator=g), torch.randn(cin, cout, 2, 2, generator=g) * 0.1, torch.randn(cout, generator=g),
+                torch.randn(b, cout, 2 * h, 2 * w, generator=g))
+
+    def run(seed):
+        from tomosar2height_amd import _lib, grid
+        x, wt, bias, gy = data(seed)
+        assert _lib.ws_bytes("t2h_upconv2x2_bx3_supported", b, h, w, cin, cout)
+        wd = _cl(wt)                                                     # [Cin][2][2][Cout] in memory
+        y = grid.upconv2x2_fwd_(_cl(x), wd, bias.to(_dev()), None, grid._empty_cl(b, cout, 2 * h, 2 * w, _dev()), True)
+        dx = grid.upconv2x2_dgrad_(_cl(gy), cout, wd, grid._empty_cl(b, cin, h, w, _dev()), True)
+        return {"y": y, "dx": dx, "wf_kn": grid.split_weights.get_up(wd, True).clone(), "wf_nk": grid.split_weights.get_up(wd, False).clone()}
+
+    def check(o, seed):
+        x, wt, bias, gy = (t.double() for t in data(seed))
+        x.requires_grad_(True)
+        want = F.conv_transpose2d(x, wt, bias, stride=2)
+        want.backward(gy)
+        _close(o["y"], want, 2e-5, "y")
+        _close(o["dx"], x.grad, 2e-5, "dx")
+    return Case(f"split-upconv2x2-{precision}-cin{cin}-cout{cout}", "SplitWeightCache.get_up, [K,N] and [N,K], under upconv2x2_fwd_ / "
+                "upconv2x2_dgrad_", run, "nan", _SPLIT_WHY, [(_SPLIT_QUERY["gemm", precision], (cin, 4 * cout), ">0")], check,
+                {"grid.CONV_PRECISION": precision}, sites=(_SPLIT_SITE,))
+
+
+def _sizing_cases():
+    """The smallest shapes at which a size query or a trailer offset can be wrong (tile builds, split-weight buffers)."""
+    cases = [_tile_case(1, 1, 2), _tile_case(1, 5, 2),
+             _tile_case(2, 2049, 64),                      # one element past a 2048 block
+             _tile_case(1, 300, 1024),                     # 2^20 cells for 300 points: the histogram part dominates
+             _tile_case(3, 257, 16),
+             _ragged_tile_case((1, 2049, 7), 16),          # max count far from both ends
+             _ragged_tile_case((3, 4097), 256),            # max ~ total
+             _ragged_tile_case((1, 1, 1, 1), 2),           # B cells >= points
+             _ragged_tile_case((600,), 1024)]
+    for precision in ("f16x2", "bf16x3"):
+        # t2h_conv3x3_bx3_supported: Cin, Cout multiples of 32 from 32; t2h_gemm_bx3_supported: K a multiple of 64 from 64, N of 32
+        # from 32 (its smallest pair already has K != N); t2h_upconv2x2_bx3_supported: Cin, Cout multiples of 64 from 64
+        cases += [_split_conv_case(32, 32, precision), _split_conv_case(32, 64, precision),
+                  _split_gemm_case(64, 32, precision), _split_gemm_case(64, 32, precision, pad=32),
+                  _split_up_case(64, 64, precision), _split_up_case(64, 128, precision)]
+    return cases
+
+
 def _cases():
     cases = [
         # coarse plan on, S = 8 (rows_per_tile >= 16 cells, C % 4 == 0); C = 12 keeps it; C = 6 and reso 16 switch it off
@@ -705,12 +892,15 @@ def _cases():
     cases.append(Case("train-step-depth4-49152", "Trainer.train_step x 2, coalesce_tiles = 1 (test_hip_model.py's bit-reproducible step)",
                       _model(True)[0], "stale", "every workspace of the step, integer ones included; the split-K, slab and "
                       "coarse-walk partials of grid.py, mlp.py:94 / :166, ops.py and deferred.py are floats only", model_queries,
-                      _model(True)[1], sites=("deferred.py:56", "deferred.py:271", "deferred.py:498", "mlp.py:693", "grid.py"),
+                      _model(True)[1],
+                      # the last two: the tile build's and the split-weight cache's buffers are banded workspaces of this step --
+                      # a refactor that allocates them by hand again takes them out of the guard, and fails here
+                      sites=("deferred.py:56", "deferred.py:271", "deferred.py:498", "mlp.py:693", "grid.py", "/tile.py:", _SPLIT_SITE),
                       nan_sites=("grid.py", "mlp.py:94", "mlp.py:166", "ops.py", "deferred.py"), loose=True))
     cases.append(Case("inference-depth4-49152", "TomoSAR2Height.forward under no_grad", _model(False)[0], "stale",
                       "as the training row", [], _model(False)[1], sites=("deferred.py:56", "grid.py"),
                       nan_sites=("grid.py", "mlp.py:94", "ops.py", "deferred.py")))
-    return cases
+    return cases + _sizing_cases()
 
 
 CASES = _cases()
@@ -763,10 +953,82 @@ def test_result_does_not_depend_on_what_the_scratch_held(case):
         for name, args, sign in case.queries:                    # the package asked THIS query and allocated what it returned
             if sign == ">0" and not case.loose and not name.endswith("_len"):
                 assert int(getattr(lib, name)(*args)) in handed, (name, args, sorted(handed)[-8:])
-        seen = " ".join(e[5] for e in g.log if e[0] == "ws")
-        assert all(s in seen for s in case.sites), (case.sites, sorted({e[5] for e in g.log if e[0] == "ws"}))
+        seen = sorted({e[5] for e in g.log if e[0] == "ws"})            # a site: a substring, or a tuple of them that all occur
+        assert all(any(_hit(s, (key,)) for s in seen) for key in case.sites), (case.sites, seen)
         print(f"{case.id}: workspaces " + ", ".join(f"{e[1]} B at {e[5].rsplit('/', 1)[-1]}" for e in g.log if e[0] == "ws")[:4000])
         assert got.keys() == clean.keys()
         for k in clean:
             assert got[k].shape == clean[k].shape and got[k].dtype == clean[k].dtype, k
             assert torch.equal(_bits(got[k]), _bits(clean[k])), f"{case.id}: {k} depends on what the scratch held before"
+
+
+# ------------------------------------------------------------------------------------------------ the batched refresh, under guard
+def _mixed_weights(seed):
+    """25 small weights, one buffer each, the six kinds in turn and two sizes of each; every fourth matrix is a column slice of a
+    wider one.  ``[(weight, cache -> its buffer)]`` in the order the cache will hold them: t2h_split_weights_batch takes 24 buffers
+    a launch, so the 25th is alone in the second."""
+    g = _gen(seed)
+    out = []
+    for i in range(25):
+        kind, big = i % 6, (i // 6) & 1
+        if kind < 2:                                                         # 3x3 [Cout,Cin,3,3], forward / transposed
+            cin, cout = (32, 64) if big else (32, 32)
+            w = _cl(torch.randn(cout, cin, 3, 3, generator=g))
+            out.append((w, lambda c, w=w, t=kind == 1: c.get(w, t)))
+        elif kind < 4:                                                       # a matrix read as [K,N] / as [N,K]
+            k, n = (64, 32) if big else (16, 64)
+            rows, cols = (k, n) if kind == 2 else (n, k)
+            w = torch.randn(rows, cols + (16 if i % 4 == 3 else 0), generator=g).to(_dev())[:, :cols]
+            out.append((w, lambda c, w=w, kn=kind == 2: c.get_gemm(w, kn)))
+        else:                                                                # ConvTranspose2d weight [Cin,Cout,2,2] as [K,N] / [N,K]
+            cin, cout = (64, 16) if big else (32, 32)
+            w = _cl(torch.randn(cin, cout, 2, 2, generator=g))
+            out.append((w, lambda c, w=w, kn=kind == 4: c.get_up(w, kn)))
+    return out
+
+
+def _refresh_twice(h2):
+    """Fill a cache, then twice: change every weight in place and ``refresh()``.  After each refresh every buffer must hold the bytes
+    of a fresh single prepare of the same weight into a new cache (test_hip_conv.py's
+    test_batched_weight_preparation_equals_the_single_calls).  Of an fp16 buffer's 256-byte trailer the words [0] and [3] are the two
+    max slots: the batch alternates between them (0 by the single prepare, then 3, then 0 again) while a fresh single prepare always
+    uses 0, so those two words hold different bytes by design -- compared are the planes and the trailer words [1] (2^-e_w) and [2] (e_w)."""
+    from tomosar2height_amd import grid
+    cache, weights = grid.SplitWeightCache(), _mixed_weights(4)
+    bufs = [get(cache) for _w, get in weights]
+    assert len(cache.entries) == 25 and len({b.data_ptr() for b in bufs}) == 25
+    snaps = []
+    for rnd in range(2):
+        with torch.no_grad():
+            for i, (w, _get) in enumerate(weights):                         # scale changes: the fp16 buffers' exponents move
+                w.mul_(1.7 + 0.25 * i) if (i + rnd) % 2 else w.add_(0.25 * (i + 1))
+        cache.refresh()
+        for i, ((_w, get), got) in enumerate(zip(weights, bufs)):
+            ref = get(grid.SplitWeightCache())
+            assert got.shape == ref.shape
+            if h2:
+                assert torch.equal(got[:-256], ref[:-256]), (rnd, i)
+                assert torch.equal(got[-256:].view(torch.int32)[1:3], ref[-256:].view(torch.int32)[1:3]), (rnd, i)
+            else:
+                assert torch.equal(got, ref), (rnd, i)
+        snaps.append([b.clone() for b in bufs])
+    return snaps
+
+
+@pytest.mark.parametrize("mode", ["f16x2", "bf16x3"])
+def test_batched_refresh_of_25_buffers_stays_inside_them(mode, monkeypatch):
+    """The seam between the two launches of a 25-buffer refresh and the fp16 trailer's max slot going 0 -> 3 -> 0, over banded
+    buffers that start from 0xFF: equal to the single prepares (``_refresh_twice``), to the unguarded run bit for bit (whole
+    buffers: both runs make the same sequence of slots), and no band damaged (checked when the block exits)."""
+    from tomosar2height_amd import grid
+    monkeypatch.setattr(grid, "CONV_PRECISION", mode)
+    clean = _refresh_twice(mode == "f16x2")
+    torch.cuda.synchronize()
+    with guarded_scratch("nan") as g:
+        got = _refresh_twice(mode == "f16x2")
+    split = [e for e in g.log if e[0] == "ws" and _hit(e[5], (_SPLIT_SITE,))]
+    assert len(split) == 25 + 2 * 25, len(split)                            # the cache's buffers and the fresh single prepares
+    assert bool((split[0][3][:split[0][4]] == 0xFF).all())                   # (they are banded)
+    for rnd in range(2):
+        for i, (a, b) in enumerate(zip(got[rnd], clean[rnd])):
+            assert torch.equal(a, b), (rnd, i)

@@ -224,7 +224,7 @@ class SplitWeightCache:
             matrix = dkind >= 2
             query, prepare, per_elem = _SPLIT_ENTRIES[matrix, h2]
             if new:
-                buf = torch.empty(int(getattr(_lib.load(), query)(a, b)), dtype=torch.uint8, device=w.device)
+                buf = _lib.workspace(int(getattr(_lib.load(), query)(a, b)), w.device)
                 e = self.entries[key] = _SplitEntry(weakref.ref(w, lambda _r, k=key: self.entries.pop(k, None)), buf)
             if matrix:                                        # (w, ldw, K, N, w_is_kn), else (w, Cin, Cout, transposed)
                 _lib.call(prepare, _lib.ptr(w), ldw, a, b, 1 if dkind == 2 else 0, _lib.ptr(e.buf), _lib.stream(), nbytes=per_elem * w.numel())

@@ -56,7 +56,7 @@ class TileIndex:
             raise ValueError("status must be an int32 [2] tensor on the points' device")
         self.status = status
         ws_bytes = _lib.ws_bytes("t2h_tile_workspace_bytes", self.B, self.N, self.nbits)
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+        ws = _lib.workspace(ws_bytes, dev)
         _lib.call("t2h_tile_build", _lib.ptr(cloud), self.dim, self.B, self.N, self.nbits, _lib.ptr(self.pts),
                   _lib.ptr(self.perm), _lib.ptr(self.cell), _lib.ptr(self.off0), _lib.ptr(self.status), _lib.ptr(ws),
                   ws_bytes, _lib.stream(), nbytes=16 * bn + 4 * cells)
@@ -97,7 +97,7 @@ class TileIndex:
             raise ValueError("status must be an int32 [2] tensor on the points' device")
         self.status = status
         ws_bytes = int(_lib.load().t2h_tile_ragged_workspace_bytes(self.B, total, max(counts), self.nbits))
-        ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=dev)
+        ws = _lib.workspace(ws_bytes, dev)
         host_starts = (ctypes.c_int32 * (self.B + 1))(*starts)
         _lib.call("t2h_tile_build_ragged", _lib.ptr(flat), in_dim, self.B, ctypes.cast(host_starts, ctypes.c_void_p), self.nbits,
                   _lib.ptr(self.pts), self.dim, _lib.ptr(self.perm), _lib.ptr(self.cell), _lib.ptr(self.off0),
