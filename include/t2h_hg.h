@@ -1,8 +1,9 @@
 /* t2h_hg.h -- C ABI of the hourglass image encoder's own kernels in libt2h_hip.so (csrc/hourglass.hip): GroupNorm statistics
  * and apply, the direct stride-2 convolution, the 2 x 2 average pool and the ConvBlock tail -- what the reference's
  * tomosar2height/encoder/hourglass.py (ConvBlock :25-82, HourGlass :85-131, HGFilter :134-218) needs beside the 3 x 3 / 1 x 1
- * convolutions and the bicubic upsampling of t2h.h.  Forward only: the encoder built on them runs for inference (DESIGN.md
- * section 4.10).
+ * convolutions and the bicubic upsampling of t2h.h -- and the adjoints of GroupNorm, of the pool and of the tail, on which
+ * ConvBlock and HourGlass train behind their `trainable` switch (the stride-2 convolution has no
+ * backward).
  *
  * Same conventions as t2h.h: device pointers owned by the caller, no allocation, no state, stream-ordered calls, 0 or a
  * negative T2H_ERR_* code, every argument validated before any launch.  The entries live in the same library but are typed by
@@ -55,6 +56,45 @@ int t2h_hg_avgpool2x2(const float *x, int B, int H, int W, int C, float *y, t2h_
  * C % 16 == 0. */
 int t2h_hg_block_tail(const float *o1, const float *o2, const float *o3, const float *res, int64_t P, int C, float *y,
                       t2h_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------------------- adjoints */
+#define T2H_HG_GNB_PIXELS 64        /* pixels of one sample per workgroup of the GroupNorm backward reduction */
+
+/* Backward of y = relu?(gamma * xhat + beta), xhat = (x - mean) * rstd with (mean, rstd) = stats[b, c / (C / G)] of
+ * t2h_hg_groupnorm_stats, given gy [B, H, W, C] = the gradient of y.  g = gy where y == NULL; else g = gy & -(y > 0): the bits of
+ * gy where y [B, H, W, C] (the forward's output after its ReLU) is positive, +0 elsewhere.  xhat is rounded as the forward rounds
+ * it (a difference, a product).  Every operation is rounded once in fp32, no fused multiply-add, no float atomic; launch
+ * boundaries are the only synchronisation.  Shapes: those of t2h_hg_groupnorm_stats with C / G <= 256.
+ *
+ * t2h_hg_groupnorm_bwd_reduce writes
+ *   dbeta[c] = sum over (b, pixel) of g,   dgamma[c] = sum over (b, pixel) of g * xhat,
+ *   gsum[b, group] = (sum over the group of g * gamma, sum over the group of g * gamma * xhat)        [B, G, 2]
+ * in this association, the same for both sums (term = g, or g * xhat rounded):  a sample's pixels are cut into chunks of
+ * T2H_HG_GNB_PIXELS consecutive pixels, chunk k = pixels 64 k ..; with L = 256 / (C / 4) lanes (integer division), lane l starts
+ * from +0 and adds the chunk's terms of pixels 64 k + l, 64 k + l + L, ... in ascending order; the chunk's partial is
+ * ((lane_0 + lane_1) + lane_2) + ...; the SAMPLE's channel sum s[b, c] starts from +0 and adds the chunk partials in ascending k
+ * (a second launch).  dbeta[c] / dgamma[c] start from +0 and add s[b, c] in ascending b.  A group sum starts from +0 and adds
+ * gamma[c] * s[b, c] (rounded) over the group's channels in ascending c: the sum over the pixels is taken before the product
+ * with gamma.  `partial` is scratch of  B * ceil(H * W / T2H_HG_GNB_PIXELS) * 2 * C  floats, any contents, overwritten. */
+int t2h_hg_groupnorm_bwd_reduce(const float *gy, const float *y, const float *x, const float *stats, const float *gamma, int B,
+                                int H, int W, int C, int G, float *partial, float *gsum, float *dbeta, float *dgamma,
+                                t2h_stream_t stream);
+
+/* dx [B, H, W, C] = rstd * ((g * gamma[c] - m1) - xhat * m2) [+ addend], m1 = gsum[b, group, 0] / n, m2 = gsum[b, group, 1] / n,
+ * n = H * W * C / G (exact in fp32); g and xhat as above.  `addend` [B, H, W, C] or NULL is added last: the gradient of another
+ * consumer of x (bn1 and bn4 of a ConvBlock normalise the same tensor; the identity residual).  dx must not overlap an input. */
+int t2h_hg_groupnorm_bwd_apply(const float *gy, const float *y, const float *x, const float *stats, const float *gamma,
+                               const float *gsum, const float *addend, int B, int H, int W, int C, int G, float *dx,
+                               t2h_stream_t stream);
+
+/* Adjoint of t2h_hg_avgpool2x2: dx [B, H, W, C], every pixel of a 2 x 2 window = gy [B, H / 2, W / 2, C] * 0.25 (exact).  H and W
+ * even. */
+int t2h_hg_avgpool2x2_bwd(const float *gy, int B, int H, int W, int C, float *dx, t2h_stream_t stream);
+
+/* Adjoint of t2h_hg_block_tail: g [P, C] copied into three DENSE tensors d1 [P, C / 2], d2 [P, C / 4], d3 [P, C / 4] -- what the
+ * 3 x 3 data and weight gradient kernels and t2h_hg_groupnorm_bwd_* (as gy or addend) take; no entry of this library reads the
+ * slices of g in place.  The gradient of `res` is g itself: no copy is made.  C % 16 == 0. */
+int t2h_hg_block_tail_bwd(const float *g, int64_t P, int C, float *d1, float *d2, float *d3, t2h_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,7 @@
 // The hourglass image encoder's own kernels (include/t2h_hg.h; reference: tomosar2height/encoder/hourglass.py): GroupNorm
 // statistics and apply, the direct stride-2 convolution (the 7 x 7 stem and the 3 x 3 hg_down = 'conv64' / 'conv128' layer), the
-// 2 x 2 average pool and the ConvBlock tail cat(out1, out2, out3) + residual.  Forward only.  fp32 NHWC throughout, 16-byte
-// accesses along C wherever C % 4 == 0 is required.
+// 2 x 2 average pool and the ConvBlock tail cat(out1, out2, out3) + residual, and the adjoints of GroupNorm, of the pool and of the
+// tail (the stride-2 convolution has none).  fp32 NHWC throughout, 16-byte accesses along C wherever C % 4 == 0 is required.
 //
 // GroupNorm statistics.  x is read once.  A workgroup of 256 threads takes a run of pixels of one sample; thread t owns the four
 // channels of float4 column t % (C / 4) and every (256 / (C / 4))-th pixel of the run, and keeps one Welford (n, mean, M2) per
@@ -13,6 +13,14 @@
 // runs give the same bytes.
 //
 // The apply kernel's ReLU is fmaxf(y, 0): no compare whose result feeds a later select.
+//
+// GroupNorm backward.  Pass 1 (gn_bwd_partial_kernel) reads gy, y and x once: a workgroup takes T2H_HG_GNB_PIXELS pixels of one
+// sample, thread t the float4 column t % (C / 4) and every (256 / (C / 4))-th pixel, and sums g and g * xhat per channel; the
+// pixel lanes are added through LDS in ascending lane order and the workgroup's two sums per channel go to `partial`.  Pass 2
+// (gn_bwd_finish_kernel, one lane per channel) adds the partials in ascending workgroup order into the sample's channel sums,
+// those over the samples into dbeta / dgamma, and gamma times those over a group's channels into the two group sums.  The
+// ReLU mask is gy & -(y > 0) by an opaque v_med3_i32 and an AND; bounds are loop limits and branches.  The association is
+// stated in include/t2h_hg.h.
 #include <math.h>
 
 #include "t2h_common.h"
@@ -22,6 +30,8 @@ namespace t2h {
 
 constexpr int kHgThreads = 256;
 constexpr int kGnChunkFloats = 65536;          // floats of one sample a statistics workgroup reads
+constexpr int kGnbPixels = T2H_HG_GNB_PIXELS;  // pixels of one sample a workgroup of the backward reduction reads
+constexpr int kGnbMaxCpg = kHgThreads;         // channels per group the backward takes (a group never straddles a finish workgroup)
 
 constexpr int kCvTile = 8;                     // output tile of the strided convolution: 8 x 8 pixels x 64 channels per workgroup
 constexpr int kCvCout = 64;
@@ -141,6 +151,149 @@ __global__ __launch_bounds__(kHgThreads) void norm_apply_kernel(const float *__r
     *reinterpret_cast<float4 *>(y + i * 4) = make_float4(r[0], r[1], r[2], r[3]);
 }
 
+// all ones where x > 0, 0 elsewhere (+-0, negative, NaN with the sign bit): -med3(bits, 0, 1) on the bits as a signed integer.
+// (the clamp is an opaque v_med3_i32: written as min(max(bits, 0), 1) the compiler may turn it into a compare and a select)
+__device__ inline unsigned hg_positive_mask(float x) {
+    int m;
+    asm("v_med3_i32 %0, %1, 0, 1" : "=v"(m) : "v"(__float_as_int(x)));
+    return (unsigned)(-m);
+}
+
+// g of the GroupNorm backward: the bits of gy where y > 0 (or everywhere: keep_all), +0 elsewhere
+__device__ inline float hg_masked(float gy, float y, unsigned keep_all) {
+    return __uint_as_float(__float_as_uint(gy) & (hg_positive_mask(y) | keep_all));
+}
+
+// grid (chunks, B).  partial [B, chunks, 2, C]: per channel, the workgroup's sums of g and of g * xhat.
+__global__ __launch_bounds__(kHgThreads) void gn_bwd_partial_kernel(const float *__restrict__ gy, const float *__restrict__ y,
+                                                                    const float *__restrict__ x, const float *__restrict__ stats,
+                                                                    int HW, int C, int G, unsigned keep_all,
+                                                                    float *__restrict__ partial) {
+    __shared__ __attribute__((aligned(16))) float s_sum[2][kHgThreads * 4];
+    const int t = threadIdx.x, b = blockIdx.y, chunk = blockIdx.x;
+    const int C4 = C >> 2, lanes = kHgThreads / C4, cpg = C / G;
+    const int c4 = t % C4, lane = t / C4;
+    float sg[4] = {0.f, 0.f, 0.f, 0.f}, sx[4] = {0.f, 0.f, 0.f, 0.f};
+    if (lane < lanes) {
+        const int p0 = chunk * kGnbPixels, p1 = min(HW, p0 + kGnbPixels);
+        const long long base = ((long long)b * HW) * C + c4 * 4;
+        float mu[4], rs[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float *st = stats + ((long long)b * G + (c4 * 4 + j) / cpg) * 2;
+            mu[j] = st[0];
+            rs[j] = st[1];
+        }
+        for (int p = p0 + lane; p < p1; p += lanes) {
+            const long long o = base + (long long)p * C;
+            const float4 g4 = *reinterpret_cast<const float4 *>(gy + o), y4 = *reinterpret_cast<const float4 *>(y + o);
+            const float4 x4 = *reinterpret_cast<const float4 *>(x + o);
+            const float gv[4] = {g4.x, g4.y, g4.z, g4.w}, yv[4] = {y4.x, y4.y, y4.z, y4.w}, xv[4] = {x4.x, x4.y, x4.z, x4.w};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float g = hg_masked(gv[j], yv[j], keep_all);
+                const float xhat = __fmul_rn(__fsub_rn(xv[j], mu[j]), rs[j]);
+                sg[j] = __fadd_rn(sg[j], g);
+                sx[j] = __fadd_rn(sx[j], __fmul_rn(g, xhat));
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { s_sum[0][t * 4 + j] = sg[j]; s_sum[1][t * 4 + j] = sx[j]; }
+    __syncthreads();
+    if (t < C4) {                                  // lane 0 of column t: its own sums, then lanes 1, 2, ... in ascending order
+        for (int l = 1; l < lanes; ++l) {
+            const int o = (l * C4 + t) * 4;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { sg[j] = __fadd_rn(sg[j], s_sum[0][o + j]); sx[j] = __fadd_rn(sx[j], s_sum[1][o + j]); }
+        }
+        float *dst = partial + (((long long)b * gridDim.x + chunk) * 2) * C + t * 4;
+        *reinterpret_cast<float4 *>(dst) = make_float4(sg[0], sg[1], sg[2], sg[3]);
+        *reinterpret_cast<float4 *>(dst + C) = make_float4(sx[0], sx[1], sx[2], sx[3]);
+    }
+}
+
+// grid (ceil(C / cb)), cb = the largest multiple of C / G up to 256: one lane per channel, whole groups per workgroup.  Per sample
+// in ascending order: the channel's two sums over the workgroups of pass 1 in ascending order from +0; added to dbeta / dgamma;
+// gamma times them through LDS to the first lane of the group, which adds the group's channels in ascending order from +0.
+__global__ __launch_bounds__(kHgThreads) void gn_bwd_finish_kernel(const float *__restrict__ partial, const float *__restrict__ gamma,
+                                                                   int B, int chunks, int C, int G, int cb, float *__restrict__ gsum,
+                                                                   float *__restrict__ dbeta, float *__restrict__ dgamma) {
+    __shared__ float ss[2][kHgThreads];
+    const int t = threadIdx.x, c = blockIdx.x * cb + t, cpg = C / G;
+    const bool live = t < cb && c < C;
+    float gm = 0.f, db = 0.f, dg = 0.f;
+    if (live) gm = gamma[c];
+    for (int b = 0; b < B; ++b) {
+        float s0 = 0.f, s1 = 0.f;
+        if (live) {
+            const float *src = partial + ((long long)b * chunks) * 2 * C + c;
+#pragma unroll 8
+            for (int k = 0; k < chunks; ++k) {
+                s0 = __fadd_rn(s0, src[(long long)k * 2 * C]);
+                s1 = __fadd_rn(s1, src[(long long)k * 2 * C + C]);
+            }
+            db = __fadd_rn(db, s0);
+            dg = __fadd_rn(dg, s1);
+        }
+        ss[0][t] = __fmul_rn(gm, s0);
+        ss[1][t] = __fmul_rn(gm, s1);
+        __syncthreads();
+        if (live && t % cpg == 0) {
+            float a0 = 0.f, a1 = 0.f;
+            for (int k = 0; k < cpg; ++k) { a0 = __fadd_rn(a0, ss[0][t + k]); a1 = __fadd_rn(a1, ss[1][t + k]); }
+            float *dst = gsum + ((long long)b * G + c / cpg) * 2;
+            dst[0] = a0;
+            dst[1] = a1;
+        }
+        __syncthreads();
+    }
+    if (live) { dbeta[c] = db; dgamma[c] = dg; }
+}
+
+// one thread per float4 of dx: dx = rstd * ((g * gamma - m1) - xhat * m2) [+ addend], m1 and m2 the group sums over n = HW * C / G
+__global__ __launch_bounds__(kHgThreads) void gn_bwd_apply_kernel(const float *__restrict__ gy, const float *__restrict__ y,
+                                                                  const float *__restrict__ x, const float *__restrict__ stats,
+                                                                  const float *__restrict__ gamma, const float *__restrict__ gsum,
+                                                                  const float *__restrict__ addend, long long total4, int HW, int C,
+                                                                  int G, unsigned keep_all, float *__restrict__ dx) {
+    const long long i = (long long)blockIdx.x * kHgThreads + threadIdx.x;
+    if (i >= total4) return;
+    const int C4 = C >> 2, cpg = C / G;
+    const int c = (int)(i % C4) * 4, b = (int)((i / C4) / HW);
+    const float n = (float)((long long)HW * cpg);
+    float mu[4], rs[4], m1[4], m2[4];
+    const bool shared = (cpg & 3) == 0;                    // (uniform) the four channels of a float4 share a group
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        if (j > 0 && shared) {
+            mu[j] = mu[0]; rs[j] = rs[0]; m1[j] = m1[0]; m2[j] = m2[0];
+            continue;
+        }
+        const long long o = ((long long)b * G + (c + j) / cpg) * 2;
+        mu[j] = stats[o];
+        rs[j] = stats[o + 1];
+        m1[j] = __fdiv_rn(gsum[o], n);
+        m2[j] = __fdiv_rn(gsum[o + 1], n);
+    }
+    const float4 g4 = *reinterpret_cast<const float4 *>(gy + i * 4), y4 = *reinterpret_cast<const float4 *>(y + i * 4);
+    const float4 x4 = *reinterpret_cast<const float4 *>(x + i * 4), w4 = *reinterpret_cast<const float4 *>(gamma + c);
+    const float gv[4] = {g4.x, g4.y, g4.z, g4.w}, yv[4] = {y4.x, y4.y, y4.z, y4.w}, xv[4] = {x4.x, x4.y, x4.z, x4.w};
+    const float wv[4] = {w4.x, w4.y, w4.z, w4.w};
+    float r[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const float g = hg_masked(gv[j], yv[j], keep_all);
+        const float xhat = __fmul_rn(__fsub_rn(xv[j], mu[j]), rs[j]);
+        r[j] = __fmul_rn(rs[j], __fsub_rn(__fsub_rn(__fmul_rn(g, wv[j]), m1[j]), __fmul_rn(xhat, m2[j])));
+    }
+    if (addend) {
+        const float4 a4 = *reinterpret_cast<const float4 *>(addend + i * 4);
+        r[0] = __fadd_rn(r[0], a4.x); r[1] = __fadd_rn(r[1], a4.y); r[2] = __fadd_rn(r[2], a4.z); r[3] = __fadd_rn(r[3], a4.w);
+    }
+    *reinterpret_cast<float4 *>(dx + i * 4) = make_float4(r[0], r[1], r[2], r[3]);
+}
+
 // grid (tiles, Cout / 64, B); thread t: channels 4 (t % 16) .. + 3 of the workgroup's 64, output row t / 32 of the tile and the
 // four columns 4 ((t / 16) % 2) .. + 3.  Per chunk of CK input channels: weights [K][K][ck][64] and the zero-padded input patch
 // [14 + K][14 + K][ck] are staged in LDS; the 16 lanes that share a pixel read the same patch word (broadcast) and 64 consecutive
@@ -247,6 +400,39 @@ __global__ __launch_bounds__(kHgThreads) void block_tail_kernel(const float *__r
     *reinterpret_cast<float4 *>(y + i * 4) = make_float4(a.x + r.x, a.y + r.y, a.z + r.z, a.w + r.w);
 }
 
+// one thread per float4 of gy [B, H / 2, W / 2, C]: gy * 0.25 to the four pixels of its window (H and W even: every pixel of dx)
+__global__ __launch_bounds__(kHgThreads) void avgpool2x2_bwd_kernel(const float *__restrict__ gy, long long total4, int H, int W, int C,
+                                                                    float *__restrict__ dx) {
+    const long long i = (long long)blockIdx.x * kHgThreads + threadIdx.x;
+    if (i >= total4) return;
+    const int C4 = C >> 2, OH = H >> 1, OW = W >> 1;
+    const int c = (int)(i % C4) * 4;
+    long long r = i / C4;
+    const int ox = (int)(r % OW);
+    r /= OW;
+    const int oy = (int)(r % OH), b = (int)(r / OH);
+    const float4 g = *reinterpret_cast<const float4 *>(gy + i * 4);
+    const float4 q = make_float4(g.x * 0.25f, g.y * 0.25f, g.z * 0.25f, g.w * 0.25f);
+    float *p = dx + ((((long long)b * H + 2 * oy) * W + 2 * ox) * C + c);
+    *reinterpret_cast<float4 *>(p) = q;
+    *reinterpret_cast<float4 *>(p + C) = q;
+    *reinterpret_cast<float4 *>(p + (long long)W * C) = q;
+    *reinterpret_cast<float4 *>(p + (long long)W * C + C) = q;
+}
+
+// one thread per float4 of g [P, C]: copied to its place in d1 [P, C / 2], d2 [P, C / 4] or d3 [P, C / 4]
+__global__ __launch_bounds__(kHgThreads) void block_tail_bwd_kernel(const float *__restrict__ g, long long total4, int C,
+                                                                    float *__restrict__ d1, float *__restrict__ d2,
+                                                                    float *__restrict__ d3) {
+    const long long i = (long long)blockIdx.x * kHgThreads + threadIdx.x;
+    if (i >= total4) return;
+    const int C4 = C >> 2, half = C >> 1, quarter = C >> 2;
+    const int c = (int)(i % C4) * 4;
+    const long long p = i / C4;
+    float *dst = c < half ? d1 + p * half + c : (c < half + quarter ? d2 + p * quarter + (c - half) : d3 + p * quarter + (c - half - quarter));
+    *reinterpret_cast<float4 *>(dst) = *reinterpret_cast<const float4 *>(g + i * 4);
+}
+
 inline bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 inline unsigned blocks_of(long long total) { return (unsigned)((total + kHgThreads - 1) / kHgThreads); }
 
@@ -264,6 +450,10 @@ bool gn_ok(int B, int H, int W, int C, int G) {
     return B >= 1 && B <= 65535 && H >= 1 && W >= 1 && (long long)H * W <= (1LL << 30) && C >= 4 && C % 4 == 0 && C <= 4 * kHgThreads &&
            G >= 1 && C % G == 0 && (long long)H * W * (C / G) <= (1LL << 24);
 }
+
+// what the GroupNorm backward takes: the forward's shapes with at most 256 channels per group
+bool gnb_ok(int B, int H, int W, int C, int G) { return gn_ok(B, H, W, C, G) && C / G <= kGnbMaxCpg; }
+inline int gnb_chunks(long long HW) { return (int)((HW + kGnbPixels - 1) / kGnbPixels); }
 
 }  // namespace
 }  // namespace t2h
@@ -356,4 +546,59 @@ T2H_API int t2h_hg_block_tail(const float *o1, const float *o2, const float *o3,
     hipLaunchKernelGGL(block_tail_kernel, dim3(blocks_of(total4)), dim3(kHgThreads), 0, as_stream(stream), o1, o2, o3, res, total4, C, y);
     note_kernel("block_tail_kernel");
     return check_launch("hg_block_tail");
+}
+
+T2H_API int t2h_hg_groupnorm_bwd_reduce(const float *gy, const float *y, const float *x, const float *stats, const float *gamma, int B,
+                                        int H, int W, int C, int G, float *partial, float *gsum, float *dbeta, float *dgamma,
+                                        t2h_stream_t stream) {
+    if (!gy || !x || !stats || !gamma || !partial || !gsum || !dbeta || !dgamma) return fail(T2H_ERR_ARG, "hg_groupnorm_bwd_reduce: null pointer");
+    if (!gnb_ok(B, H, W, C, G))
+        return fail(T2H_ERR_ARG, "hg_groupnorm_bwd_reduce: no kernel for B=%d H=%d W=%d C=%d G=%d (C %% 4 == 0, C <= 1024, C %% G == 0, "
+                    "C / G <= 256, at most 2^24 elements per group)", B, H, W, C, G);
+    if (!al16(gy) || (y && !al16(y)) || !al16(x) || !al16(partial)) return fail(T2H_ERR_ARG, "hg_groupnorm_bwd_reduce: gy, y, x, partial must be 16-byte aligned");
+    const int HW = H * W, chunks = gnb_chunks(HW), cpg = C / G, cb = (kHgThreads / cpg) * cpg;
+    hipStream_t s = as_stream(stream);
+    hipLaunchKernelGGL(gn_bwd_partial_kernel, dim3((unsigned)chunks, (unsigned)B), dim3(kHgThreads), 0, s, gy, y ? y : gy, x, stats, HW, C, G,
+                       y ? 0u : 0xffffffffu, partial);
+    hipLaunchKernelGGL(gn_bwd_finish_kernel, dim3((unsigned)((C + cb - 1) / cb)), dim3(kHgThreads), 0, s, partial, gamma, B, chunks, C, G, cb,
+                       gsum, dbeta, dgamma);
+    note_kernel("gn_bwd_partial_kernel");
+    return check_launch("hg_groupnorm_bwd_reduce");
+}
+
+T2H_API int t2h_hg_groupnorm_bwd_apply(const float *gy, const float *y, const float *x, const float *stats, const float *gamma,
+                                       const float *gsum, const float *addend, int B, int H, int W, int C, int G, float *dx,
+                                       t2h_stream_t stream) {
+    if (!gy || !x || !stats || !gamma || !gsum || !dx) return fail(T2H_ERR_ARG, "hg_groupnorm_bwd_apply: null pointer");
+    if (!gnb_ok(B, H, W, C, G))
+        return fail(T2H_ERR_ARG, "hg_groupnorm_bwd_apply: no kernel for B=%d H=%d W=%d C=%d G=%d (C %% 4 == 0, C <= 1024, C %% G == 0, "
+                    "C / G <= 256, at most 2^24 elements per group)", B, H, W, C, G);
+    if (!al16(gy) || (y && !al16(y)) || !al16(x) || !al16(gamma) || (addend && !al16(addend)) || !al16(dx))
+        return fail(T2H_ERR_ARG, "hg_groupnorm_bwd_apply: gy, y, x, gamma, addend, dx must be 16-byte aligned");
+    const long long total4 = (long long)B * H * W * (C / 4);
+    hipLaunchKernelGGL(gn_bwd_apply_kernel, dim3(blocks_of(total4)), dim3(kHgThreads), 0, as_stream(stream), gy, y ? y : gy, x, stats, gamma,
+                       gsum, addend, total4, H * W, C, G, y ? 0u : 0xffffffffu, dx);
+    note_kernel("gn_bwd_apply_kernel");
+    return check_launch("hg_groupnorm_bwd_apply");
+}
+
+T2H_API int t2h_hg_avgpool2x2_bwd(const float *gy, int B, int H, int W, int C, float *dx, t2h_stream_t stream) {
+    if (!gy || !dx) return fail(T2H_ERR_ARG, "hg_avgpool2x2_bwd: null pointer");
+    if (int rc = check_plane("hg_avgpool2x2_bwd", B, H, W, C)) return rc;
+    if (H < 2 || W < 2 || H % 2 != 0 || W % 2 != 0) return fail(T2H_ERR_ARG, "hg_avgpool2x2_bwd: H=%d, W=%d must be even, at least 2", H, W);
+    if (!al16(gy) || !al16(dx)) return fail(T2H_ERR_ARG, "hg_avgpool2x2_bwd: pointers must be 16-byte aligned");
+    const long long total4 = (long long)B * (H / 2) * (W / 2) * (C / 4);
+    hipLaunchKernelGGL(avgpool2x2_bwd_kernel, dim3(blocks_of(total4)), dim3(kHgThreads), 0, as_stream(stream), gy, total4, H, W, C, dx);
+    note_kernel("avgpool2x2_bwd_kernel");
+    return check_launch("hg_avgpool2x2_bwd");
+}
+
+T2H_API int t2h_hg_block_tail_bwd(const float *g, int64_t P, int C, float *d1, float *d2, float *d3, t2h_stream_t stream) {
+    if (!g || !d1 || !d2 || !d3) return fail(T2H_ERR_ARG, "hg_block_tail_bwd: null pointer");
+    if (P < 1 || C < 16 || C % 16 != 0 || P * (int64_t)C > (1LL << 40)) return fail(T2H_ERR_ARG, "hg_block_tail_bwd: bad shape P=%lld C=%d (C %% 16 == 0)", (long long)P, C);
+    if (!al16(g) || !al16(d1) || !al16(d2) || !al16(d3)) return fail(T2H_ERR_ARG, "hg_block_tail_bwd: pointers must be 16-byte aligned");
+    const long long total4 = (long long)P * (C / 4);
+    hipLaunchKernelGGL(block_tail_bwd_kernel, dim3(blocks_of(total4)), dim3(kHgThreads), 0, as_stream(stream), g, total4, C, d1, d2, d3);
+    note_kernel("block_tail_bwd_kernel");
+    return check_launch("hg_block_tail_bwd");
 }

@@ -1,5 +1,5 @@
-"""HGFilter, the stacked-hourglass image encoder (reference: tomosar2height/encoder/hourglass.py:25-218), on the MI355X path, for
-inference.
+"""HGFilter, the stacked-hourglass image encoder (reference: tomosar2height/encoder/hourglass.py:25-218), on the MI355X path: for
+inference by default, and with ``trainable=True`` (``norm='group'``) with gradients for everything behind the stem.
 
 Constructor signatures, defaults, attribute names and ``state_dict`` keys and shapes are the reference's -- ``bn4`` is also
 ``downsample.0`` (both keys, one storage) and exists unused when ``in_planes == out_planes``; the ``add_module`` names are
@@ -14,10 +14,21 @@ on csrc/hourglass.hip (include/t2h_hg.h, bound here: ``_lib.declare``).  ``bn1``
 tensor with the same groups: one statistics pass serves both.  The kernels have no NCHW form: an NCHW input is converted at the
 module boundary, whatever ``TomoSAR2Height.set_channels_last`` says, and the output is channels_last memory.
 
-Inference only (DESIGN.md sections 4.10 and 8).  The forward builds no autograd graph.  It raises ``NotImplementedError`` when
-gradients are enabled and a parameter of the module requires one, and for ``norm='batch'`` under ``train()`` (batch statistics);
-``norm='group'`` computes the same thing in either mode.  H and W of every plane must be powers of two (the 3 x 3 kernels), for
-``HGFilter`` at least ``4 * 2 ** num_hourglass``: a ``ValueError`` before any launch otherwise.
+Inference only by default (DESIGN.md sections 4.10 and 8).  The forward builds no autograd graph.  It raises
+``NotImplementedError`` when gradients are enabled and a parameter of the module requires one, and for ``norm='batch'`` under
+``train()`` (batch statistics); ``norm='group'`` computes the same thing in either mode.  H and W of every plane must be powers
+of two (the 3 x 3 kernels), for ``HGFilter`` at least ``4 * 2 ** num_hourglass``: a ``ValueError`` before any launch otherwise.
+
+Training is opt-in: ``ConvBlock``, ``HourGlass`` and ``HGFilter`` take a keyword-only ``trainable=False`` (a plain attribute, no
+parameter or buffer; setting it on a module sets it on the hourglass modules below it).  With ``trainable=True``, ``norm='group'``
+and gradients enabled the forward builds an autograd graph of ``_GroupNorm`` (GroupNorm [+ ReLU], ``t2h_hg_groupnorm_bwd_*``),
+``grid._Conv3x3``, ``grid.conv1x1`` with its addend, ``_AvgPool2x2``, ``_BlockTail`` and ``_Upsample2xAdd``; gradients reach every
+parameter and the input, in ``train()`` and ``eval()`` alike.  A tensor with two consumers inside a block (the block's input:
+bn1, bn4 and the identity residual; out1 and out2: the next norm and the tail) gets the sum of their gradients in the GroupNorm
+backward's addend, not in a pass of its own.  Under ``torch.no_grad()`` the inference path runs unchanged.  Not built, refused
+before any launch: ``norm='batch'`` with ``trainable=True`` in either mode; for ``HGFilter`` a stem that requires a gradient --
+``conv1``, and ``down_conv2`` of ``hg_down='conv64' / 'conv128'`` (the stride-2 convolution has no weight / data gradient), so
+the image gets none either; and ``Trainer`` refuses a model whose image encoder is trainable.
 """
 import ctypes
 
@@ -36,22 +47,28 @@ SIGNATURES = {
     "t2h_hg_conv_s2_fwd": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "t2h_hg_avgpool2x2": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "t2h_hg_block_tail": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _vp, _vp]),
+    "t2h_hg_groupnorm_bwd_reduce": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "t2h_hg_groupnorm_bwd_apply": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "t2h_hg_avgpool2x2_bwd": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "t2h_hg_block_tail_bwd": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp]),
 }
+GNB_PIXELS = 64              # T2H_HG_GNB_PIXELS: pixels of one sample per workgroup of the GroupNorm backward reduction
 
 _lib.declare("t2h_hg.h", SIGNATURES)
 load = _lib.load
 
 
 # ------------------------------------------------------------------------------------------------ kernels
-def _plane(x: torch.Tensor, what: str) -> torch.Tensor:
-    """``x`` [B, C, H, W] float32 on the device, as a dense NHWC tensor (an NCHW input is converted here)."""
+def _plane(x: torch.Tensor, what: str, detach: bool = True) -> torch.Tensor:
+    """``x`` [B, C, H, W] float32 on the device, as a dense NHWC tensor (an NCHW input is converted here); ``detach=False``: with
+    its place in the autograd graph (the trainable path)."""
     if not isinstance(x, torch.Tensor) or x.dim() != 4:
         raise ValueError(f"{what}: expected a [B, C, H, W] tensor")
     if not x.is_cuda:
         raise RuntimeError(f"{what}: expected a tensor on the MI355X (cuda device), got {x.device}: tomosar2height_amd has no CPU path")
     if x.dtype != torch.float32:
         raise TypeError(f"{what}: float32 expected, got {x.dtype}")
-    return grid._as_cl(x.detach())
+    return grid._as_cl(x.detach() if detach else x)
 
 
 def group_norm_stats(x: torch.Tensor, groups: int, eps: float) -> torch.Tensor:
@@ -115,6 +132,151 @@ def upsample2x_bicubic_add(x: torch.Tensor, addend: torch.Tensor) -> torch.Tenso
     return y
 
 
+# ------------------------------------------------------------------------------------------------ adjoints
+def gn_bwd_partial_floats(b: int, h: int, w: int, c: int) -> int:
+    """Floats of the ``partial`` scratch of ``t2h_hg_groupnorm_bwd_reduce`` (the formula of include/t2h_hg.h)."""
+    return b * (-(-(h * w) // GNB_PIXELS)) * 2 * c
+
+
+def group_norm_bwd_reduce(gy, y, x, stats, gamma):
+    """(gsum [B, G, 2], dbeta [C], dgamma [C]) of GroupNorm's backward; ``y``: the forward's output when a ReLU followed, else
+    None.  ``gy``, ``y``, ``x``: channels_last planes; ``stats``: what ``group_norm_stats`` returned for ``x``."""
+    b, c, h, w = x.shape
+    groups = stats.shape[1]
+    partial = torch.empty(gn_bwd_partial_floats(b, h, w, c), dtype=torch.float32, device=x.device)
+    gsum = torch.empty(b, groups, 2, dtype=torch.float32, device=x.device)
+    dbeta, dgamma = torch.empty(c, dtype=torch.float32, device=x.device), torch.empty(c, dtype=torch.float32, device=x.device)
+    _lib.call("t2h_hg_groupnorm_bwd_reduce", _lib.ptr(gy), _lib.ptr(y) if y is not None else None, _lib.ptr(x), _lib.ptr(stats),
+              _lib.ptr(gamma), b, h, w, c, groups, _lib.ptr(partial), _lib.ptr(gsum), _lib.ptr(dbeta), _lib.ptr(dgamma), _lib.stream(),
+              nbytes=4 * x.numel() * (3 if y is not None else 2))
+    return gsum, dbeta, dgamma
+
+
+def group_norm_bwd_apply(gy, y, x, stats, gamma, gsum, addend=None) -> torch.Tensor:
+    """dx of GroupNorm's backward [+ addend] from the group sums of ``group_norm_bwd_reduce``."""
+    b, c, h, w = x.shape
+    dx = grid._empty_cl(b, c, h, w, x.device)
+    _lib.call("t2h_hg_groupnorm_bwd_apply", _lib.ptr(gy), _lib.ptr(y) if y is not None else None, _lib.ptr(x), _lib.ptr(stats),
+              _lib.ptr(gamma), _lib.ptr(gsum), _lib.ptr(addend) if addend is not None else None, b, h, w, c, stats.shape[1], _lib.ptr(dx),
+              _lib.stream(), nbytes=4 * x.numel() * (3 + (y is not None) + (addend is not None)))
+    return dx
+
+
+def avgpool2x2_bwd(gy: torch.Tensor, h: int, w: int) -> torch.Tensor:
+    b, c = gy.shape[:2]
+    dx = grid._empty_cl(b, c, h, w, gy.device)
+    _lib.call("t2h_hg_avgpool2x2_bwd", _lib.ptr(gy), b, h, w, c, _lib.ptr(dx), _lib.stream(), nbytes=4 * (gy.numel() + dx.numel()))
+    return dx
+
+
+def block_tail_bwd(g: torch.Tensor):
+    """The gradients of ``o1``, ``o2`` and ``o3`` of ``block_tail`` as three dense planes (that of ``res`` is ``g`` itself)."""
+    b, c, h, w = g.shape
+    d1, d2, d3 = (grid._empty_cl(b, n, h, w, g.device) for n in (c // 2, c // 4, c // 4))
+    _lib.call("t2h_hg_block_tail_bwd", _lib.ptr(g), b * h * w, c, _lib.ptr(d1), _lib.ptr(d2), _lib.ptr(d3), _lib.stream(),
+              nbytes=8 * g.numel())
+    return d1, d2, d3
+
+
+class _GroupNorm(torch.autograd.Function):
+    """``relu?(GroupNorm(x))`` for one or two (weight, bias) pairs over the same statistics -- ``bn1`` and ``bn4`` of a ConvBlock --:
+    one output per pair and, ``thru``, ``x`` again (an alias) for another consumer of it.  The backward hands the gradient of
+    that consumer, then each pair's dx, on as the next pair's addend: ``x`` gets the sum without a pass that only adds."""
+
+    @staticmethod
+    def forward(ctx, x, groups: int, eps: float, relu: bool, thru: bool, *affine):
+        x = grid._as_cl(x)
+        stats = group_norm_stats(x, groups, eps)
+        ys = tuple(norm_apply(x, stats, affine[k], affine[k + 1], groups, relu) for k in range(0, len(affine), 2))
+        ctx.save_for_backward(x, stats, *affine[0::2], *(ys if relu else ()))
+        ctx.conf = (relu, thru, len(ys))
+        ctx.set_materialize_grads(False)
+        return ys + ((grid._alias(x),) if thru else ())
+
+    @staticmethod
+    def backward(ctx, *grads):
+        relu, thru, n = ctx.conf
+        x, stats = ctx.saved_tensors[:2]
+        gammas = ctx.saved_tensors[2:2 + n]
+        ys = ctx.saved_tensors[2 + n:] if relu else (None,) * n
+        need_dx = ctx.needs_input_grad[0]
+        dx = grid._as_cl(grads[n]) if thru and grads[n] is not None else None
+        out = [None] * (2 * n)
+        for k in reversed(range(n)):
+            if grads[k] is None:
+                continue
+            gy = grid._as_cl(grads[k])
+            gsum, out[2 * k + 1], out[2 * k] = group_norm_bwd_reduce(gy, ys[k], x, stats, gammas[k])
+            if need_dx:
+                dx = group_norm_bwd_apply(gy, ys[k], x, stats, gammas[k], gsum, dx)
+        return (dx if need_dx else None, None, None, None, None) + tuple(out)
+
+
+class _AvgPool2x2(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        x = grid._as_cl(x)
+        ctx.hw = (x.shape[2], x.shape[3])
+        return avgpool2x2(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return avgpool2x2_bwd(grid._as_cl(g), *ctx.hw)
+
+
+class _BlockTail(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, o1, o2, o3, res):
+        return block_tail(grid._as_cl(o1), grid._as_cl(o2), grid._as_cl(o3), grid._as_cl(res))
+
+    @staticmethod
+    def backward(ctx, g):
+        g = grid._as_cl(g)
+        return block_tail_bwd(g) + (g,)
+
+
+class _Upsample2xAdd(torch.autograd.Function):
+    """``addend + bicubic x 2 (align_corners=True) of x`` on channels_last planes of any H x W (``ops.upsample_bicubic`` is the same
+    pair of kernels for square outputs); the backward is the deterministic gather, the addend's gradient is ``g`` itself."""
+
+    @staticmethod
+    def forward(ctx, x, addend):
+        x, addend = grid._as_cl(x), grid._as_cl(addend)
+        ctx.shape = tuple(x.shape)
+        return upsample2x_bicubic_add(x, addend)
+
+    @staticmethod
+    def backward(ctx, g):
+        b, c, h, w = ctx.shape
+        g = grid._as_cl(g)
+        gin = grid._empty_cl(b, c, h, w, g.device)
+        _lib.call("t2h_upsample_bicubic_bwd", _lib.ptr(g), b, c, h, w, 2 * h, 2 * w, 1, _lib.ptr(gin), _lib.stream(),
+                  nbytes=4 * (g.numel() + gin.numel()))
+        return gin, g
+
+
+def group_norm(x: torch.Tensor, layer: nn.GroupNorm, relu: bool = False) -> torch.Tensor:
+    """``relu?(layer(x))``, differentiable with respect to ``x`` and the layer's weight and bias."""
+    x = _plane(x, "group_norm", detach=False)
+    return _GroupNorm.apply(x, layer.num_groups, layer.eps, bool(relu), False, layer.weight, layer.bias)[0]
+
+
+def avg_pool2x2(x: torch.Tensor) -> torch.Tensor:
+    """``F.avg_pool2d(x, 2, stride=2)`` for even H and W, differentiable."""
+    x = _plane(x, "avg_pool2x2", detach=False)
+    if x.shape[2] % 2 or x.shape[3] % 2:
+        raise ValueError(f"avg_pool2x2: H={x.shape[2]}, W={x.shape[3]} must be even (the adjoint writes whole windows)")
+    return _AvgPool2x2.apply(x)
+
+
+def conv_block_tail(o1, o2, o3, res) -> torch.Tensor:
+    """``cat(o1, o2, o3, dim=1) + res``, differentiable."""
+    o1, o2, o3, res = (_plane(t, "conv_block_tail", detach=False) for t in (o1, o2, o3, res))
+    if (o1.shape[1], o2.shape[1], o3.shape[1]) != (res.shape[1] // 2, res.shape[1] // 4, res.shape[1] // 4):
+        raise ValueError("conv_block_tail: inputs of C / 2, C / 4 and C / 4 channels expected")
+    return _BlockTail.apply(o1, o2, o3, res)
+
+
 # ------------------------------------------------------------------------------------------------ module plumbing
 def _require_inference(module: nn.Module, what: str):
     if torch.is_grad_enabled() and any(p.requires_grad for p in module.parameters()):
@@ -132,6 +294,46 @@ def _check_planes(x, what, min_h, min_w):
 
 
 class _HGModule(nn.Module):
+    @property
+    def trainable(self) -> bool:
+        """The opt-in switch of the autograd path (a plain attribute: no parameter, no buffer, nothing in the ``state_dict``);
+        setting it sets it on every hourglass module below this one."""
+        return self.__dict__.get("_hg_trainable", False)
+
+    @trainable.setter
+    def trainable(self, flag: bool):
+        self.__dict__["_hg_trainable"] = bool(flag)
+        for child in self.children():
+            if isinstance(child, _HGModule):
+                child.trainable = flag
+
+    def _builds_graph(self, what: str) -> bool:
+        """True when this forward is the trainable one: the switch is on and gradients are enabled."""
+        if not self.trainable:
+            return False
+        if any(isinstance(m, nn.BatchNorm2d) for m in self.modules()):
+            raise NotImplementedError(f"{what}(trainable=True) with norm='batch' is not built, in train() or eval(): neither the "
+                                      "frozen-BatchNorm backward nor batch statistics (norm='group' trains)")
+        return torch.is_grad_enabled()
+
+    def _gn(self, x, names, thru=False):
+        """``_GroupNorm`` + ReLU of ``x`` for the GroupNorm attributes ``names`` (one, or two over the same statistics)."""
+        layers = [getattr(self, n) for n in names]
+        affine = [p for layer in layers for p in (layer.weight, layer.bias)]
+        return _GroupNorm.apply(x, layers[0].num_groups, layers[0].eps, True, thru, *affine)
+
+    def _conv3x3_grad(self, x, conv):
+        self._weight_cl(conv)
+        if not grid.conv3x3_supported(x, conv):
+            raise NotImplementedError(f"no 3 x 3 kernel for {conv.in_channels} -> {conv.out_channels} channels on a {tuple(x.shape[2:])} plane")
+        return grid._Conv3x3.apply(x, conv.weight, conv.bias, False, False, False)
+
+    @staticmethod
+    def _weight_cl(conv):
+        if not conv.weight.permute(0, 2, 3, 1).is_contiguous():          # the kernels read [Cout][3][3][Cin]: re-laid once, in place
+            conv.weight.data = conv.weight.data.contiguous(memory_format=torch.channels_last)
+        return conv.weight
+
     def _derived(self) -> _lib.Derived:
         d = self.__dict__.get("_hg_derived")
         if d is None:
@@ -157,10 +359,7 @@ class _HGModule(nn.Module):
         return norm_apply(x, None, scale, shift, 1, relu)
 
     def _conv3x3(self, x, conv):
-        w = conv.weight
-        if not w.permute(0, 2, 3, 1).is_contiguous():          # the kernels read [Cout][3][3][Cin]: re-laid once, in place
-            conv.weight.data = w.data.contiguous(memory_format=torch.channels_last)
-            w = conv.weight
+        w = self._weight_cl(conv)
         b, _, h, wd = x.shape
         y = grid._empty_cl(b, w.shape[0], h, wd, x.device)
         return grid.conv3x3_fwd_(x, w, conv.bias, y)
@@ -172,8 +371,9 @@ class _HGModule(nn.Module):
 
 
 class ConvBlock(_HGModule):
-    def __init__(self, in_planes, out_planes, norm="batch"):
+    def __init__(self, in_planes, out_planes, norm="batch", *, trainable: bool = False):
         super().__init__()
+        self.trainable = trainable
         self.conv1 = nn.Conv2d(in_planes, int(out_planes / 2), 3, 1, 1, bias=False)
         self.conv2 = nn.Conv2d(int(out_planes / 2), int(out_planes / 4), 3, 1, 1, bias=False)
         self.conv3 = nn.Conv2d(int(out_planes / 4), int(out_planes / 4), 3, 1, 1, bias=False)
@@ -202,7 +402,26 @@ class ConvBlock(_HGModule):
             residual = grid.conv1x1(self._norm(x, "bn4", True, stats), self.downsample[2])
         return block_tail(out1, out2, out3, residual)
 
+    def _fwd_grad(self, x):
+        """``_fwd`` as an autograd graph (``norm='group'``).  ``x``, ``out1`` and ``out2`` each have two consumers: the second one
+        takes the alias the ``_GroupNorm`` returns, whose gradient that backward adds in its own pass."""
+        if self.downsample is not None:
+            y1, y4 = self._gn(x, ("bn1", "bn4"))
+            residual = grid.conv1x1(y4, self.downsample[2])
+        else:
+            y1, residual = self._gn(x, ("bn1",), thru=True)
+        out1 = self._conv3x3_grad(y1, self.conv1)
+        y2, out1 = self._gn(out1, ("bn2",), thru=True)
+        out2 = self._conv3x3_grad(y2, self.conv2)
+        y3, out2 = self._gn(out2, ("bn3",), thru=True)
+        out3 = self._conv3x3_grad(y3, self.conv3)
+        return _BlockTail.apply(out1, out2, out3, residual)
+
     def forward(self, x):
+        if self._builds_graph("ConvBlock"):
+            x = _plane(x, "ConvBlock", detach=False)
+            _check_planes(x, "ConvBlock", 1, 1)
+            return self._fwd_grad(x)
         _require_inference(self, "ConvBlock")
         x = _plane(x, "ConvBlock")
         _check_planes(x, "ConvBlock", 1, 1)
@@ -211,10 +430,11 @@ class ConvBlock(_HGModule):
 
 
 class HourGlass(_HGModule):
-    def __init__(self, num_modules, depth, num_features, norm="batch"):
+    def __init__(self, num_modules, depth, num_features, norm="batch", *, trainable: bool = False):
         super().__init__()
         self.num_modules, self.depth, self.features, self.norm = num_modules, depth, num_features, norm
         self._generate_network(self.depth)
+        self.trainable = trainable
 
     def _generate_network(self, level):
         self.add_module("b1_" + str(level), ConvBlock(self.features, self.features, norm=self.norm))
@@ -232,7 +452,18 @@ class HourGlass(_HGModule):
         low3 = self._modules["b3_" + str(level)]._fwd(low2)
         return upsample2x_bicubic_add(low3, up1)
 
+    def _fwd_grad(self, level, inp):
+        up1 = self._modules["b1_" + str(level)]._fwd_grad(inp)
+        low1 = self._modules["b2_" + str(level)]._fwd_grad(_AvgPool2x2.apply(inp))
+        low2 = self._fwd_grad(level - 1, low1) if level > 1 else self._modules["b2_plus_" + str(level)]._fwd_grad(low1)
+        low3 = self._modules["b3_" + str(level)]._fwd_grad(low2)
+        return _Upsample2xAdd.apply(low3, up1)
+
     def forward(self, x):
+        if self._builds_graph("HourGlass"):
+            x = _plane(x, "HourGlass", detach=False)
+            _check_planes(x, "HourGlass", 2 ** self.depth, 2 ** self.depth)
+            return self._fwd_grad(self.depth, x)
         _require_inference(self, "HourGlass")
         x = _plane(x, "HourGlass")
         _check_planes(x, "HourGlass", 2 ** self.depth, 2 ** self.depth)
@@ -241,7 +472,8 @@ class HourGlass(_HGModule):
 
 
 class HGFilter(_HGModule):
-    def __init__(self, in_channel, feature_dim=256, num_hourglass=2, num_stack=4, norm="group", hg_down="ave_pool"):
+    def __init__(self, in_channel, feature_dim=256, num_hourglass=2, num_stack=4, norm="group", hg_down="ave_pool", *,
+                 trainable: bool = False):
         super().__init__()
         self.in_channel = in_channel
         self.out_feature_dim = feature_dim
@@ -278,10 +510,61 @@ class HGFilter(_HGModule):
             if i < self.num_modules - 1:
                 self.add_module("bl" + str(i), nn.Conv2d(256, 256, kernel_size=1, stride=1, padding=0))
                 self.add_module("al" + str(i), nn.Conv2d(self.out_feature_dim, 256, kernel_size=1, stride=1, padding=0))
+        self.trainable = trainable
+
+    def _frozen_stem(self):
+        """The layers the trainable forward runs without a graph: ``conv1`` -- and, where ``down_conv2`` follows, everything up to it,
+        since what lies in front of a stride-2 convolution would need its data gradient."""
+        names = ("conv1",) if self.hg_down == "ave_pool" else ("conv1", "bn1", "conv2", "down_conv2")
+        wants = [f"{n}.{k}" for n in names for k, p in getattr(self, n).named_parameters() if p.requires_grad]
+        if wants:
+            raise NotImplementedError(f"HGFilter(trainable=True) runs with a frozen stem: {', '.join(wants)} require a gradient, but the "
+                                      "stride-2 convolution's weight / data gradient is not built (conv1"
+                                      + ("" if self.hg_down == "ave_pool" else ", down_conv2 and what lies in front of it")
+                                      + "); call requires_grad_(False) on them")
+
+    def _fwd_grad(self, x, rec):
+        m = self._modules
+        with torch.no_grad():
+            x = self._conv_s2(x, "conv1")
+            if self.hg_down != "ave_pool":
+                x = self._norm(x, "bn1", True)
+                rec("stem", x)
+                x = self.conv2._fwd(x)
+                rec("conv2", x)
+                x = self._conv_s2(x, "down_conv2")
+        if self.hg_down == "ave_pool":
+            x = self._gn(x, ("bn1",))[0]
+            rec("stem", x)
+            x = self.conv2._fwd_grad(x)
+            rec("conv2", x)
+            x = _AvgPool2x2.apply(x)
+        x = self.conv3._fwd_grad(x)
+        rec("conv3", x)
+        x = self.conv4._fwd_grad(x)
+        rec("conv4", x)
+        previous, tmp_out = x, None
+        for i in range(self.num_modules):
+            hg = m["m" + str(i)]._fwd_grad(self.num_hourglass, previous)
+            ll = m["top_m_" + str(i)]._fwd_grad(hg)
+            ll = self._gn(grid.conv1x1(ll, m["conv_last" + str(i)]), ("bn_end" + str(i),))[0]
+            tmp_out = grid.conv1x1(ll, m["l" + str(i)])
+            rec(f"hg{i}", hg), rec(f"ll{i}", ll), rec(f"tmp_out{i}", tmp_out)
+            if i < self.num_modules - 1:
+                previous = grid.conv1x1(tmp_out, m["al" + str(i)], grid.conv1x1(ll, m["bl" + str(i)], previous))
+        return tmp_out
 
     def forward(self, x, trace: dict = None):
         """``x`` [B, in_channel, H, W] -> [B, feature_dim, H / 4, W / 4] (channels_last memory).  ``trace``: a dict that receives
         ``stem``, ``conv2``, ``conv3``, ``conv4`` and per stack ``hg{i}``, ``ll{i}``, ``tmp_out{i}``."""
+        if self._builds_graph("HGFilter"):
+            self._frozen_stem()
+            x = _plane(x, "HGFilter")                      # (detached: the image gets no gradient)
+            if x.shape[1] != self.in_channel:
+                raise ValueError(f"HGFilter: {self.in_channel} input channels expected, got {x.shape[1]}")
+            low = 4 * 2 ** self.num_hourglass
+            _check_planes(x, "HGFilter", low, low)
+            return self._fwd_grad(x, (lambda k, v: trace.__setitem__(k, v)) if trace is not None else (lambda k, v: None))
         _require_inference(self, "HGFilter")
         x = _plane(x, "HGFilter")
         if x.shape[1] != self.in_channel:

@@ -70,6 +70,10 @@ class Trainer:
                  use_footprint=False, weight_ce=10., process_group=None, check_domain=True, scheduler=None):
         """``check_domain``: at every optimizer step (one device read per ``optimize_every`` tiles) raise if any input
         point was outside [0, 1)^2 -- the reference's scatter would index out of range for such a point."""
+        if getattr(getattr(model, "image_encoder", None), "trainable", False):
+            raise NotImplementedError("Trainer: an image encoder with trainable=True (encoder/hourglass.py) is not supported: its "
+                                      "backward is not part of the tile pipeline, the side streams, the direct gradient accumulation "
+                                      "or the captured graphs -- train it with plain autograd, or construct it with trainable=False")
         self.model = model
         self.optimizer = optimizer
         self.device = device
