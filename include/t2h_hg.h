@@ -1,9 +1,9 @@
 /* t2h_hg.h -- C ABI of the hourglass image encoder's own kernels in libt2h_hip.so (csrc/hourglass.hip): GroupNorm statistics
  * and apply, the direct stride-2 convolution, the 2 x 2 average pool and the ConvBlock tail -- what the reference's
  * tomosar2height/encoder/hourglass.py (ConvBlock :25-82, HourGlass :85-131, HGFilter :134-218) needs beside the 3 x 3 / 1 x 1
- * convolutions and the bicubic upsampling of t2h.h -- and the adjoints of GroupNorm, of the pool and of the tail, on which
- * ConvBlock and HourGlass train behind their `trainable` switch (the stride-2 convolution has no
- * backward).
+ * convolutions and the bicubic upsampling of t2h.h -- and the adjoints of GroupNorm, of the pool, of the tail and of the stride-2
+ * convolution, on which ConvBlock, HourGlass and HGFilter train behind their `trainable` / `stem_gradients` switches (DESIGN.md
+ * section 4.10).
  *
  * Same conventions as t2h.h: device pointers owned by the caller, no allocation, no state, stream-ordered calls, 0 or a
  * negative T2H_ERR_* code, every argument validated before any launch.  The entries live in the same library but are typed by
@@ -95,6 +95,38 @@ int t2h_hg_avgpool2x2_bwd(const float *gy, int B, int H, int W, int C, float *dx
  * 3 x 3 data and weight gradient kernels and t2h_hg_groupnorm_bwd_* (as gy or addend) take; no entry of this library reads the
  * slices of g in place.  The gradient of `res` is g itself: no copy is made.  C % 16 == 0. */
 int t2h_hg_block_tail_bwd(const float *g, int64_t P, int C, float *d1, float *d2, float *d3, t2h_stream_t stream);
+
+/* ------------------------------------------------------------------------- adjoints of the stride-2 convolution */
+#define T2H_CS2_SLAB_ROWS 8         /* output rows ...                                                             */
+#define T2H_CS2_SLAB_COLS 32        /* ... and columns of one sample that one workgroup of the weight gradient sums */
+
+/* Both adjoints take the shapes of t2h_hg_conv_s2_fwd (K odd <= 7, pad <= K / 2, Cout % 64 == 0, any Cin >= 1, H + 2 pad >= K,
+ * W + 2 pad >= K; anything else: T2H_ERR_ARG before a launch), the forward's weight layout [K][K][Cin][Cout] and, with
+ * OH = (H + 2 pad - K) / 2 + 1 (OW likewise), gy [B, OH, OW, Cout].  fp32 fused multiply-adds (v_fma_f32), no float atomic, no
+ * zero-fill pass: two runs give the same bytes.
+ *
+ * Data gradient: dx [B, H, W, Cin] = [addend +] sum over (ky, kx, co) of gy[b, oy, ox, co] * w[ky, kx, ci, co] over the taps with
+ * iy + pad - ky = 2 oy, ix + pad - kx = 2 ox, 0 <= oy < OH, 0 <= ox < OW -- a gather: every element of dx is written exactly once,
+ * an element no tap reaches (the last row when H + 2 pad - K is odd) is +0, or the addend (an addend of -0 gives +0).  One sum is
+ * ONE chain of fused multiply-adds from +0, in this order: chunks of CK output channels ascending (what fits the staging buffers: CK = 16 for a
+ * 3 x 3 layer of more than 16 input channels, 8 for the 7 x 7 stem), then the kernel rows of the parity of iy + pad ascending, then the kernel
+ * columns of the parity of ix + pad ascending, then the chunk's output channels ascending; `addend` [B, H, W, Cin] or NULL (the
+ * gradient of another consumer of x) is added last.  gy and w 16-byte aligned; dx and addend too when Cin % 4 == 0, else 4-byte.
+ * dx must not overlap an input. */
+int t2h_hg_conv_s2_dgrad(const float *gy, const float *w, const float *addend, float *dx, int B, int H, int W, int Cin, int Cout,
+                         int K, int pad, t2h_stream_t stream);
+
+/* Weight gradient: dw [K][K][Cin][Cout] = sum over (b, oy, ox) of x[b, 2 oy + ky - pad, 2 ox + kx - pad, ci] * gy[b, oy, ox, co]
+ * (zero padding), dbias [Cout] = sum over (b, oy, ox) of gy (dbias may be NULL), in this association, the same for every
+ * element: a sample's output pixels are cut into slabs of T2H_CS2_SLAB_ROWS x T2H_CS2_SLAB_COLS pixels, slab (sy, sx) = rows
+ * 8 sy .., columns 32 sx ..; the slab's partial starts from +0 and adds its terms -- by one fused multiply-add each for dw, one
+ * addition each for dbias -- over the slab's 8 x 8 tiles from left to right and the 64 pixels of a tile in row-major order (a pixel
+ * outside the plane, or of the padding, counts as zero); a second launch starts from +0 and adds the slab partials in ascending
+ * (b, sy, sx).  `partial` is scratch of
+ *   B * ceil(OH / T2H_CS2_SLAB_ROWS) * ceil(OW / T2H_CS2_SLAB_COLS) * (K * K * Cin + 1) * Cout  floats,
+ * any contents, overwritten (per slab the rows of dw, then dbias).  gy, partial, dw, dbias 16-byte aligned, x 4-byte. */
+int t2h_hg_conv_s2_wgrad(const float *x, const float *gy, float *partial, float *dw, float *dbias, int B, int H, int W, int Cin,
+                         int Cout, int K, int pad, t2h_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,7 +1,8 @@
 // The hourglass image encoder's own kernels (include/t2h_hg.h; reference: tomosar2height/encoder/hourglass.py): GroupNorm
 // statistics and apply, the direct stride-2 convolution (the 7 x 7 stem and the 3 x 3 hg_down = 'conv64' / 'conv128' layer), the
-// 2 x 2 average pool and the ConvBlock tail cat(out1, out2, out3) + residual, and the adjoints of GroupNorm, of the pool and of the
-// tail (the stride-2 convolution has none).  fp32 NHWC throughout, 16-byte accesses along C wherever C % 4 == 0 is required.
+// 2 x 2 average pool and the ConvBlock tail cat(out1, out2, out3) + residual, and the adjoints of GroupNorm, of the pool, of the
+// tail and of the stride-2 convolution (a gather over four parity classes for dx, slab-reduced dw: described at the kernels).
+// fp32 NHWC throughout, 16-byte accesses along C wherever C % 4 == 0 is required.
 //
 // GroupNorm statistics.  x is read once.  A workgroup of 256 threads takes a run of pixels of one sample; thread t owns the four
 // channels of float4 column t % (C / 4) and every (256 / (C / 4))-th pixel of the run, and keeps one Welford (n, mean, M2) per
@@ -37,6 +38,14 @@ constexpr int kCvTile = 8;                     // output tile of the strided con
 constexpr int kCvCout = 64;
 constexpr int kCvWMax = 7 * 7 * 3 * kCvCout;   // floats of weights staged at a time: the whole 7 x 7 x 3 stem, 16 channels of a 3 x 3
 constexpr int kCvPMax = 17 * 17 * 16;          // floats of input patch staged at a time (3 x 3: 17 x 17 x 16; 7 x 7: 21 x 21 x 3)
+
+constexpr int kDgWFloats = 9 * 16 * 68;        // data gradient: floats of transposed weights staged at a time (3 x 3, 16 output channels, 64 + 4 input channels)
+constexpr int kDgPFloats = 6144;               // ... and of gy patch (7 x 7 stem: 19 x 35 pixels x (8 | 1) output channels)
+constexpr int kWgRows = 10;                    // weight gradient: weight rows (tap, input channel) per thread, 16 kWgRows per workgroup
+constexpr int kWgPFloats = kCvPMax;            // ... floats of input patch staged at a time (the forward's patches)
+constexpr int kWgSlabRows = T2H_CS2_SLAB_ROWS; // ... output pixels of one slab
+constexpr int kWgSlabCols = T2H_CS2_SLAB_COLS;
+static_assert(kWgSlabRows == kCvTile && kWgSlabCols % kCvTile == 0, "a slab is a row of whole 8 x 8 tiles");
 
 namespace {
 
@@ -433,6 +442,215 @@ __global__ __launch_bounds__(kHgThreads) void block_tail_bwd_kernel(const float 
     *reinterpret_cast<float4 *>(dst) = *reinterpret_cast<const float4 *>(g + i * 4);
 }
 
+// ---------------------------------------------------------------------------------- stride-2 convolution: data gradient
+// One kernel row / column pair of one parity class of the data gradient for a thread's two q-blocks (a q-block = the 2 x 2 input
+// pixels with (iy + pad) / 2 = qy, (ix + pad) / 2 = qx; class = 2 py + px, the parities of iy + pad and ix + pad): over the staged
+// output channels in ascending order, acc += gy * w by one fused multiply-add each.  NY / NX: the tap pair also has a kernel
+// row 2 a + 1 / a kernel column 2 c + 1 (a template argument: a loop bound of the caller, never a per-lane value).
+template <bool NY, bool NX>
+__device__ inline void dgrad_taps(float (&acc)[2][4][4], const float *g0, int PS, const float *wk, int WS, int row_step, int ck) {
+    for (int co = 0; co < ck; ++co) {
+        const float g[2] = {g0[co], g0[PS + co]};
+        const float *wc = wk + co * WS;
+#pragma unroll
+        for (int cls = 0; cls < 4; ++cls) {
+            if ((cls >= 2 && !NY) || ((cls & 1) && !NX)) continue;
+            const float4 wv = *reinterpret_cast<const float4 *>(wc + (cls >> 1) * row_step + (cls & 1) * ck * WS);
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                acc[q][cls][0] = fmaf(g[q], wv.x, acc[q][cls][0]);
+                acc[q][cls][1] = fmaf(g[q], wv.y, acc[q][cls][1]);
+                acc[q][cls][2] = fmaf(g[q], wv.z, acc[q][cls][2]);
+                acc[q][cls][3] = fmaf(g[q], wv.w, acc[q][cls][3]);
+            }
+        }
+    }
+}
+
+// grid (tiles, ceil(Cin / (4 CG)), B).  CG = 16: a workgroup takes 64 input channels and 4 x 8 q-blocks (8 x 16 pixels), the 16
+// lanes of a pixel group hold consecutive float4s of channels (Cin = 128); CG = 1: 4 input channels and 16 x 32 q-blocks, every lane
+// another pixel group (Cin = 3).  Thread: two q-blocks side by side x the four parity classes x 4 channels.  Per chunk of CK output
+// channels the weights, transposed to [K][K][ck][4 CG (+ 4)] (input channels contiguous; zero past Cin), and the zero-padded gy
+// patch [S + A - 1][2 S + A - 1][ck | 1], A = (K + 1) / 2, are staged in LDS: borders and parity are the patch's zeros and the
+// loop bounds.  A gather: every dx element is written once, by the thread that summed it.
+template <int CG>
+__global__ __launch_bounds__(kHgThreads) void conv_s2_dgrad_kernel(const float *__restrict__ gy, const float *__restrict__ w,
+                                                                   const float *__restrict__ addend, float *__restrict__ dx, int H,
+                                                                   int W, int Cin, int Cout, int OH, int OW, int K, int pad, int CK,
+                                                                   int tiles_x, int vec) {
+    constexpr int S = CG == 16 ? 4 : 16, CIT = 4 * CG, WS = CIT + 4;
+    __shared__ __attribute__((aligned(16))) float sw[kDgWFloats];
+    __shared__ float sg[kDgPFloats];
+    const int t = threadIdx.x, cg = t % CG, pg = t / CG, qyl = pg / S, qxl = 2 * (pg % S);
+    const int A = (K + 1) / 2, PWX = 2 * S + A - 1, PWY = S + A - 1;
+    const int q0y = (blockIdx.x / tiles_x) * S, q0x = (blockIdx.x % tiles_x) * 2 * S;
+    const int ci0 = blockIdx.y * CIT, b = blockIdx.z;
+    float acc[2][4][4];
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+#pragma unroll
+        for (int cls = 0; cls < 4; ++cls)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[q][cls][j] = 0.f;
+    for (int c0 = 0; c0 < Cout; c0 += CK) {
+        const int ck = min(CK, Cout - c0), PS = ck | 1;
+        __syncthreads();
+        const int nw = K * K * ck * CIT;
+        for (int i = t; i < nw; i += kHgThreads) {
+            const int co = i % ck, r = i / ck, ci = r % CIT, kk = r / CIT;
+            float v = 0.f;
+            if (ci0 + ci < Cin) v = w[((long long)kk * Cin + ci0 + ci) * Cout + c0 + co];
+            sw[(kk * ck + co) * WS + ci] = v;
+        }
+        const int np = PWY * PWX * ck;
+        for (int i = t; i < np; i += kHgThreads) {
+            const int co = i % ck, r = i / ck, cx = r % PWX, ry = r / PWX;
+            const int oy = q0y - (A - 1) + ry, ox = q0x - (A - 1) + cx;
+            float v = 0.f;
+            if (oy >= 0 && oy < OH && ox >= 0 && ox < OW) v = gy[(((long long)b * OH + oy) * OW + ox) * Cout + c0 + co];
+            sg[r * PS + co] = v;
+        }
+        __syncthreads();
+        for (int a = 0; a < A; ++a) {                  // kernel rows 2 a (+ 1) meet output row qy - a
+            for (int c = 0; c < A; ++c) {
+                const float *g0 = sg + ((qyl + A - 1 - a) * PWX + (qxl + A - 1 - c)) * PS;
+                const float *wk = sw + ((2 * a * K + 2 * c) * ck) * WS + cg * 4;
+                const int row_step = K * ck * WS;
+                const bool ny = 2 * a + 1 < K, nx = 2 * c + 1 < K;
+                if (ny && nx) dgrad_taps<true, true>(acc, g0, PS, wk, WS, row_step, ck);
+                else if (ny) dgrad_taps<true, false>(acc, g0, PS, wk, WS, row_step, ck);
+                else if (nx) dgrad_taps<false, true>(acc, g0, PS, wk, WS, row_step, ck);
+                else dgrad_taps<false, false>(acc, g0, PS, wk, WS, row_step, ck);
+            }
+        }
+    }
+    const int ci = ci0 + cg * 4;
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+#pragma unroll
+        for (int cls = 0; cls < 4; ++cls) {
+            const int iy = 2 * (q0y + qyl) + (cls >> 1) - pad, ix = 2 * (q0x + qxl + q) + (cls & 1) - pad;
+            if (iy < 0 || iy >= H || ix < 0 || ix >= W) continue;
+            const long long o = (((long long)b * H + iy) * W + ix) * Cin + ci;
+            if (vec) {
+                if (ci < Cin) {
+                    float4 r = make_float4(acc[q][cls][0], acc[q][cls][1], acc[q][cls][2], acc[q][cls][3]);
+                    if (addend) {
+                        const float4 a4 = *reinterpret_cast<const float4 *>(addend + o);
+                        r = make_float4(r.x + a4.x, r.y + a4.y, r.z + a4.z, r.w + a4.w);
+                    }
+                    *reinterpret_cast<float4 *>(dx + o) = r;
+                }
+            } else {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    if (ci + j < Cin) {
+                        float r = acc[q][cls][j];
+                        if (addend) r += addend[o + j];
+                        dx[o + j] = r;
+                    }
+                }
+            }
+        }
+    }
+}
+
+// -------------------------------------------------------------------------------- stride-2 convolution: weight gradient
+// grid (slabs of a sample, chunks of input channels x Cout / 64, B).  A workgroup owns one slab -- T2H_CS2_SLAB_ROWS x
+// T2H_CS2_SLAB_COLS output pixels of one sample, up to four 8 x 8 tiles side by side --, CK input channels and 64 output channels.
+// Thread t: output channels 4 (t % 16) .. + 3 and the kWgRows weight rows m = t / 16 + 16 r of the chunk's K K ck rows
+// (m = (ky K + kx) ck + ci).  Per tile the gy tile [64][64] (zero outside the plane) and the zero-padded x patch
+// [14 + K][14 + K][ck] are staged in LDS; a row past the chunk reads row K K ck - 1 again and is not stored.  Every sum is one
+// chain of fused multiply-adds from +0 over the slab's tiles from left to right and a tile's 64 pixels in row-major order.
+__global__ __launch_bounds__(kHgThreads) void conv_s2_wgrad_kernel(const float *__restrict__ x, const float *__restrict__ gy,
+                                                                   float *__restrict__ partial, int H, int W, int Cin, int Cout, int OH,
+                                                                   int OW, int K, int pad, int CK, int slabs_x, int co_tiles) {
+    __shared__ __attribute__((aligned(16))) float sgy[kCvTile * kCvTile * kCvCout];
+    __shared__ float sp[kWgPFloats];
+    const int t = threadIdx.x, cg = t & 15, mg = t >> 4;
+    const int chunk = blockIdx.y / co_tiles, co0 = (blockIdx.y % co_tiles) * kCvCout, b = blockIdx.z;
+    const int c0 = chunk * CK, ck = min(CK, Cin - c0), M = K * K * ck, PW = 2 * kCvTile + K - 2;
+    const int oy0 = (blockIdx.x / slabs_x) * kWgSlabRows, sx0 = (blockIdx.x % slabs_x) * kWgSlabCols;
+    // row m of the chunk -> its offset inside the patch of a pixel, and its row of dw: tabulated by loops over the taps (uniform
+    // counters and a branch; a per-lane m / ck would assemble to compares kept for selects)
+    __shared__ int s_off[16 * kWgRows], s_row[16 * kWgRows];
+    for (int ky = 0, kk = 0; ky < K; ++ky)
+        for (int kx = 0; kx < K; ++kx, ++kk)
+            if (t < ck) {
+                s_off[kk * ck + t] = (ky * PW + kx) * ck + t;
+                s_row[kk * ck + t] = kk * Cin + c0 + t;
+            }
+    __syncthreads();
+    int off[kWgRows];
+#pragma unroll
+    for (int r = 0; r < kWgRows; ++r) off[r] = s_off[min(mg + 16 * r, M - 1)];
+    float acc[kWgRows][4], bsum[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int r = 0; r < kWgRows; ++r)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[r][j] = 0.f;
+    for (int ox0 = sx0; ox0 < min(OW, sx0 + kWgSlabCols); ox0 += kCvTile) {
+        __syncthreads();
+        for (int i = t; i < kCvTile * kCvTile * (kCvCout / 4); i += kHgThreads) {
+            const int p = i / (kCvCout / 4), c4 = i % (kCvCout / 4);
+            const int oy = oy0 + p / kCvTile, ox = ox0 + p % kCvTile;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (oy < OH && ox < OW) v = *reinterpret_cast<const float4 *>(gy + (((long long)b * OH + oy) * OW + ox) * Cout + co0 + c4 * 4);
+            *reinterpret_cast<float4 *>(sgy + i * 4) = v;
+        }
+        const int np = PW * PW * ck, iy0 = 2 * oy0 - pad, ix0 = 2 * ox0 - pad;
+        for (int i = t; i < np; i += kHgThreads) {
+            const int ci = i % ck, r = i / ck, px = r % PW, py = r / PW;
+            const int iy = iy0 + py, ix = ix0 + px;
+            float v = 0.f;
+            if (iy >= 0 && iy < H && ix >= 0 && ix < W) v = x[(((long long)b * H + iy) * W + ix) * Cin + c0 + ci];
+            sp[i] = v;
+        }
+        __syncthreads();
+#pragma unroll 1
+        for (int py = 0; py < kCvTile; ++py) {
+#pragma unroll 2
+            for (int px = 0; px < kCvTile; ++px) {
+                const float4 g = *reinterpret_cast<const float4 *>(sgy + (py * kCvTile + px) * kCvCout + cg * 4);
+                const float *xp = sp + (2 * py * PW + 2 * px) * ck;
+                bsum[0] += g.x; bsum[1] += g.y; bsum[2] += g.z; bsum[3] += g.w;
+#pragma unroll
+                for (int r = 0; r < kWgRows; ++r) {
+                    const float xv = xp[off[r]];
+                    acc[r][0] = fmaf(xv, g.x, acc[r][0]);
+                    acc[r][1] = fmaf(xv, g.y, acc[r][1]);
+                    acc[r][2] = fmaf(xv, g.z, acc[r][2]);
+                    acc[r][3] = fmaf(xv, g.w, acc[r][3]);
+                }
+            }
+        }
+    }
+    const long long rows = (long long)K * K * Cin + 1;
+    float *dst = partial + ((long long)b * gridDim.x + blockIdx.x) * rows * Cout + co0 + cg * 4;
+#pragma unroll
+    for (int r = 0; r < kWgRows; ++r) {
+        const int m = mg + 16 * r;
+        if (m < M) *reinterpret_cast<float4 *>(dst + (long long)s_row[m] * Cout) = make_float4(acc[r][0], acc[r][1], acc[r][2], acc[r][3]);
+    }
+    if (chunk == 0 && mg == 0) *reinterpret_cast<float4 *>(dst + (rows - 1) * Cout) = make_float4(bsum[0], bsum[1], bsum[2], bsum[3]);
+}
+
+// one thread per float4 of (dw, dbias) = the K K Cin + 1 rows of a slab: the slabs added in ascending order from +0
+__global__ __launch_bounds__(kHgThreads) void conv_s2_wgrad_reduce_kernel(const float *__restrict__ partial, int slabs, long long total4,
+                                                                          long long dw4, float *__restrict__ dw, float *__restrict__ dbias) {
+    const long long i = (long long)blockIdx.x * kHgThreads + threadIdx.x;
+    if (i >= total4) return;
+    float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    const float4 *src = reinterpret_cast<const float4 *>(partial) + i;
+#pragma unroll 4
+    for (int k = 0; k < slabs; ++k) {
+        const float4 v = src[(long long)k * total4];
+        s = make_float4(s.x + v.x, s.y + v.y, s.z + v.z, s.w + v.w);
+    }
+    if (i < dw4) *reinterpret_cast<float4 *>(dw + i * 4) = s;
+    else if (dbias) *reinterpret_cast<float4 *>(dbias + (i - dw4) * 4) = s;
+}
+
 inline bool al16(const void *p) { return ((uintptr_t)p & 15) == 0; }
 inline unsigned blocks_of(long long total) { return (unsigned)((total + kHgThreads - 1) / kHgThreads); }
 
@@ -454,6 +672,16 @@ bool gn_ok(int B, int H, int W, int C, int G) {
 // what the GroupNorm backward takes: the forward's shapes with at most 256 channels per group
 bool gnb_ok(int B, int H, int W, int C, int G) { return gn_ok(B, H, W, C, G) && C / G <= kGnbMaxCpg; }
 inline int gnb_chunks(long long HW) { return (int)((HW + kGnbPixels - 1) / kGnbPixels); }
+
+// the domain of t2h_hg_conv_s2_fwd, for its two adjoints
+int check_conv_s2(const char *what, int B, int H, int W, int Cin, int Cout, int K, int pad) {
+    if (B < 1 || B > 65535 || H < 1 || W < 1 || H > 32768 || W > 32768 || Cin < 1 || Cin > 4096)
+        return fail(T2H_ERR_ARG, "%s: bad shape B=%d H=%d W=%d Cin=%d", what, B, H, W, Cin);
+    if (K < 1 || K > 7 || K % 2 == 0 || pad < 0 || pad > K / 2 || Cout < kCvCout || Cout % kCvCout != 0 || Cout / kCvCout > 65535)
+        return fail(T2H_ERR_ARG, "%s: no kernel for K=%d pad=%d Cout=%d (K odd <= 7, pad <= K / 2, Cout %% 64 == 0)", what, K, pad, Cout);
+    if (H + 2 * pad < K || W + 2 * pad < K) return fail(T2H_ERR_ARG, "%s: the plane is smaller than the kernel", what);
+    return T2H_OK;
+}
 
 }  // namespace
 }  // namespace t2h
@@ -601,4 +829,55 @@ T2H_API int t2h_hg_block_tail_bwd(const float *g, int64_t P, int C, float *d1, f
     hipLaunchKernelGGL(block_tail_bwd_kernel, dim3(blocks_of(total4)), dim3(kHgThreads), 0, as_stream(stream), g, total4, C, d1, d2, d3);
     note_kernel("block_tail_bwd_kernel");
     return check_launch("hg_block_tail_bwd");
+}
+
+T2H_API int t2h_hg_conv_s2_dgrad(const float *gy, const float *w, const float *addend, float *dx, int B, int H, int W, int Cin, int Cout,
+                                 int K, int pad, t2h_stream_t stream) {
+    if (!gy || !w || !dx) return fail(T2H_ERR_ARG, "hg_conv_s2_dgrad: null pointer");
+    if (int rc = check_conv_s2("hg_conv_s2_dgrad", B, H, W, Cin, Cout, K, pad)) return rc;
+    if (!al16(gy) || !al16(w) || ((uintptr_t)dx & 3) || ((uintptr_t)addend & 3) || (Cin % 4 == 0 && (!al16(dx) || !al16(addend))))
+        return fail(T2H_ERR_ARG, "hg_conv_s2_dgrad: gy, w (and, Cin %% 4 == 0, dx and addend) must be 16-byte aligned");
+    const int OH = (H + 2 * pad - K) / 2 + 1, OW = (W + 2 * pad - K) / 2 + 1, A = (K + 1) / 2;
+    const bool wide = Cin > 16;                          // lanes over channels (64 per workgroup), else lanes over pixels (4)
+    const int S = wide ? 4 : 16, WS = (wide ? 64 : 4) + 4;
+    int CK = 16;
+    while (CK > 1 && (K * K * CK * WS > kDgWFloats || (S + A - 1) * (2 * S + A - 1) * (CK | 1) > kDgPFloats)) CK >>= 1;
+    if (K * K * CK * WS > kDgWFloats || (S + A - 1) * (2 * S + A - 1) * (CK | 1) > kDgPFloats)
+        return fail(T2H_ERR_ARG, "hg_conv_s2_dgrad: K=%d does not fit the staging buffers", K);
+    const int qy = (H + pad - 1) / 2 + 1, qx = (W + pad - 1) / 2 + 1;          // q-blocks that hold a pixel of the plane
+    const int tiles_y = (qy + S - 1) / S, tiles_x = (qx + 2 * S - 1) / (2 * S), cit = wide ? 64 : 4;
+    const dim3 grid((unsigned)(tiles_x * tiles_y), (unsigned)((Cin + cit - 1) / cit), (unsigned)B);
+    if (wide)
+        hipLaunchKernelGGL(conv_s2_dgrad_kernel<16>, grid, dim3(kHgThreads), 0, as_stream(stream), gy, w, addend, dx, H, W, Cin, Cout, OH, OW,
+                           K, pad, CK, tiles_x, Cin % 4 == 0 ? 1 : 0);
+    else
+        hipLaunchKernelGGL(conv_s2_dgrad_kernel<1>, grid, dim3(kHgThreads), 0, as_stream(stream), gy, w, addend, dx, H, W, Cin, Cout, OH, OW,
+                           K, pad, CK, tiles_x, Cin % 4 == 0 ? 1 : 0);
+    note_kernel("conv_s2_dgrad_kernel");
+    return check_launch("hg_conv_s2_dgrad");
+}
+
+T2H_API int t2h_hg_conv_s2_wgrad(const float *x, const float *gy, float *partial, float *dw, float *dbias, int B, int H, int W, int Cin,
+                                 int Cout, int K, int pad, t2h_stream_t stream) {
+    if (!x || !gy || !partial || !dw) return fail(T2H_ERR_ARG, "hg_conv_s2_wgrad: null pointer");
+    if (int rc = check_conv_s2("hg_conv_s2_wgrad", B, H, W, Cin, Cout, K, pad)) return rc;
+    if (!al16(gy) || !al16(partial) || !al16(dw) || (dbias && !al16(dbias)) || ((uintptr_t)x & 3))
+        return fail(T2H_ERR_ARG, "hg_conv_s2_wgrad: gy, partial, dw, dbias must be 16-byte aligned");
+    const int OH = (H + 2 * pad - K) / 2 + 1, OW = (W + 2 * pad - K) / 2 + 1, PW = 2 * kCvTile + K - 2;
+    int CK = 16 * kWgRows / (K * K);
+    if (CK > 16) CK = 16;
+    if (CK > Cin) CK = Cin;
+    if (CK < 1 || PW * PW * CK > kWgPFloats) return fail(T2H_ERR_ARG, "hg_conv_s2_wgrad: K=%d does not fit the staging buffers", K);
+    const int slabs_y = (OH + kWgSlabRows - 1) / kWgSlabRows, slabs_x = (OW + kWgSlabCols - 1) / kWgSlabCols;
+    const int chunks = (Cin + CK - 1) / CK, co_tiles = Cout / kCvCout;
+    const long long slabs = (long long)B * slabs_y * slabs_x, total4 = ((long long)K * K * Cin + 1) * (Cout / 4);
+    if ((long long)chunks * co_tiles > 65535 || slabs > (1 << 24) || total4 > (1LL << 31) * kHgThreads / 2)
+        return fail(T2H_ERR_ARG, "hg_conv_s2_wgrad: shape too large (B=%d H=%d W=%d Cin=%d Cout=%d)", B, H, W, Cin, Cout);
+    hipStream_t s = as_stream(stream);
+    hipLaunchKernelGGL(conv_s2_wgrad_kernel, dim3((unsigned)(slabs_y * slabs_x), (unsigned)(chunks * co_tiles), (unsigned)B), dim3(kHgThreads), 0,
+                       s, x, gy, partial, H, W, Cin, Cout, OH, OW, K, pad, CK, slabs_x, co_tiles);
+    hipLaunchKernelGGL(conv_s2_wgrad_reduce_kernel, dim3(blocks_of(total4)), dim3(kHgThreads), 0, s, partial, (int)slabs, total4,
+                       (long long)K * K * Cin * (Cout / 4), dw, dbias);
+    note_kernel("conv_s2_wgrad_kernel");
+    return check_launch("hg_conv_s2_wgrad");
 }

@@ -27,8 +27,15 @@ parameter and the input, in ``train()`` and ``eval()`` alike.  A tensor with two
 bn1, bn4 and the identity residual; out1 and out2: the next norm and the tail) gets the sum of their gradients in the GroupNorm
 backward's addend, not in a pass of its own.  Under ``torch.no_grad()`` the inference path runs unchanged.  Not built, refused
 before any launch: ``norm='batch'`` with ``trainable=True`` in either mode; for ``HGFilter`` a stem that requires a gradient --
-``conv1``, and ``down_conv2`` of ``hg_down='conv64' / 'conv128'`` (the stride-2 convolution has no weight / data gradient), so
-the image gets none either; and ``Trainer`` refuses a model whose image encoder is trainable.
+``conv1``, and ``down_conv2`` of ``hg_down='conv64' / 'conv128'``, so the image gets none either; and ``Trainer`` refuses a model
+whose image encoder is trainable.
+
+The stem trains behind a second keyword-only switch of ``HGFilter``, ``stem_gradients=False`` (a plain attribute too; read by the
+trainable forward only, so it can ride ``model.encoder2_kwargs``).  With ``trainable=True, stem_gradients=True`` the stem is part
+of the graph: ``conv1`` and ``down_conv2`` run through ``_ConvS2`` (``t2h_hg_conv_s2_dgrad`` / ``_wgrad``: the data gradient
+only for an input that needs one, the weight gradient only for a weight or bias that does), ``bn1`` through ``_GroupNorm``,
+``conv2`` through its own graph, and an image with ``requires_grad`` gets ``.grad``.  Switched off, every path and message above
+is unchanged.  ``conv2d_stride2`` is the differentiable stride-2 convolution on its own.
 """
 import ctypes
 
@@ -51,8 +58,11 @@ SIGNATURES = {
     "t2h_hg_groupnorm_bwd_apply": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "t2h_hg_avgpool2x2_bwd": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
     "t2h_hg_block_tail_bwd": (_i, [_vp, _i64, _i, _vp, _vp, _vp, _vp]),
+    "t2h_hg_conv_s2_dgrad": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "t2h_hg_conv_s2_wgrad": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
 }
 GNB_PIXELS = 64              # T2H_HG_GNB_PIXELS: pixels of one sample per workgroup of the GroupNorm backward reduction
+CS2_SLAB_ROWS, CS2_SLAB_COLS = 8, 32     # T2H_CS2_SLAB_ROWS / _COLS: output pixels of one slab of the stride-2 weight gradient
 
 _lib.declare("t2h_hg.h", SIGNATURES)
 load = _lib.load
@@ -178,6 +188,68 @@ def block_tail_bwd(g: torch.Tensor):
     return d1, d2, d3
 
 
+def conv_s2_wgrad_partial_floats(b: int, h: int, w: int, cin: int, cout: int, k: int, pad: int) -> int:
+    """Floats of the ``partial`` scratch of ``t2h_hg_conv_s2_wgrad`` (the formula of include/t2h_hg.h)."""
+    oh, ow = (h + 2 * pad - k) // 2 + 1, (w + 2 * pad - k) // 2 + 1
+    return b * (-(-oh // CS2_SLAB_ROWS)) * (-(-ow // CS2_SLAB_COLS)) * (k * k * cin + 1) * cout
+
+
+def conv_s2_dgrad(gy: torch.Tensor, w_kkio: torch.Tensor, h: int, w: int, k: int, pad: int, addend=None) -> torch.Tensor:
+    """dx [B, Cin, H, W] (channels_last) of ``conv_s2`` [+ addend] from ``gy``, the channels_last gradient of its output."""
+    b, cout = gy.shape[:2]
+    cin = w_kkio.shape[2]
+    if tuple(w_kkio.shape) != (k, k, cin, cout):
+        raise ValueError(f"conv_s2_dgrad: a [{k}, {k}, Cin, {cout}] weight expected for this gy, got {tuple(w_kkio.shape)}")
+    if k % 2 and 0 <= 2 * pad <= k and tuple(gy.shape[2:]) != ((h + 2 * pad - k) // 2 + 1, (w + 2 * pad - k) // 2 + 1):
+        raise ValueError(f"conv_s2_dgrad: gy {tuple(gy.shape)} is not the output of a {h} x {w} plane")
+    dx = grid._empty_cl(b, cin, h, w, gy.device)
+    _lib.call("t2h_hg_conv_s2_dgrad", _lib.ptr(gy), _lib.ptr(w_kkio), _lib.ptr(addend) if addend is not None else None, _lib.ptr(dx),
+              b, h, w, cin, cout, k, pad, _lib.stream(), nbytes=4 * (gy.numel() + w_kkio.numel() + dx.numel() * (1 + (addend is not None))),
+              flops=2 * k * k * cin * cout * gy.shape[0] * gy.shape[2] * gy.shape[3])
+    return dx
+
+
+def conv_s2_wgrad(x: torch.Tensor, gy: torch.Tensor, k: int, pad: int, with_bias: bool = True):
+    """(dw [K, K, Cin, Cout], dbias [Cout] or None) of ``conv_s2`` from its channels_last input and output gradient."""
+    b, cin, h, w = x.shape
+    cout = gy.shape[1]
+    if gy.shape[0] != b or (k % 2 and 0 <= 2 * pad <= k and tuple(gy.shape[2:]) != ((h + 2 * pad - k) // 2 + 1, (w + 2 * pad - k) // 2 + 1)):
+        raise ValueError(f"conv_s2_wgrad: gy {tuple(gy.shape)} is not the output of x {tuple(x.shape)}")
+    dw = torch.empty(k, k, cin, cout, dtype=torch.float32, device=x.device)
+    dbias = torch.empty(cout, dtype=torch.float32, device=x.device) if with_bias else None
+    floats = conv_s2_wgrad_partial_floats(b, h, w, cin, cout, k, pad)
+    partial = _lib.workspace(4 * floats, x.device)
+    _lib.call("t2h_hg_conv_s2_wgrad", _lib.ptr(x), _lib.ptr(gy), _lib.ptr(partial), _lib.ptr(dw), _lib.ptr(dbias) if with_bias else None,
+              b, h, w, cin, cout, k, pad, _lib.stream(), nbytes=4 * (x.numel() + gy.numel() + 2 * floats + dw.numel()),
+              flops=2 * k * k * cin * cout * b * gy.shape[2] * gy.shape[3])
+    return dw, dbias
+
+
+class _ConvS2(torch.autograd.Function):
+    """``conv_s2`` of a K x K / stride 2 ``nn.Conv2d`` weight [Cout, Cin, K, K] with its adjoints: the data gradient only when the
+    input needs one (not for the stem's image), the weight gradient only for a weight or a bias that does."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias, w_kkio, pad: int):
+        x = grid._as_cl(x)
+        ctx.save_for_backward(x, w_kkio)
+        ctx.conf = (weight.shape[2], pad, bias is not None)
+        return conv_s2(x, w_kkio, bias, weight.shape[2], pad)
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, w_kkio = ctx.saved_tensors
+        k, pad, has_bias = ctx.conf
+        need_x, need_w, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[2]
+        gy = grid._as_cl(gy)
+        dx = conv_s2_dgrad(gy, w_kkio, x.shape[2], x.shape[3], k, pad) if need_x else None
+        dw = db = None
+        if need_w or need_b:
+            dw, db = conv_s2_wgrad(x, gy, k, pad, with_bias=need_b)
+            dw = dw.permute(3, 2, 0, 1).contiguous() if need_w else None          # the parameter's own [Cout, Cin, K, K]
+        return dx, dw, db, None, None
+
+
 class _GroupNorm(torch.autograd.Function):
     """``relu?(GroupNorm(x))`` for one or two (weight, bias) pairs over the same statistics -- ``bn1`` and ``bn4`` of a ConvBlock --:
     one output per pair and, ``thru``, ``x`` again (an alias) for another consumer of it.  The backward hands the gradient of
@@ -267,6 +339,16 @@ def avg_pool2x2(x: torch.Tensor) -> torch.Tensor:
     if x.shape[2] % 2 or x.shape[3] % 2:
         raise ValueError(f"avg_pool2x2: H={x.shape[2]}, W={x.shape[3]} must be even (the adjoint writes whole windows)")
     return _AvgPool2x2.apply(x)
+
+
+def conv2d_stride2(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor = None, padding: int = 0) -> torch.Tensor:
+    """``F.conv2d(x, weight, bias, stride=2, padding=padding)`` for an odd K <= 7, ``padding <= K // 2`` and ``Cout % 64 == 0``,
+    differentiable with respect to ``x``, ``weight`` and ``bias`` (``weight``: [Cout, Cin, K, K] as ``nn.Conv2d`` keeps it; it is
+    re-laid to [K, K, Cin, Cout] on every call -- the modules cache that per weight version)."""
+    x = _plane(x, "conv2d_stride2", detach=False)
+    if weight.dim() != 4 or weight.shape[2] != weight.shape[3] or weight.shape[1] != x.shape[1]:
+        raise ValueError(f"conv2d_stride2: a [Cout, {x.shape[1]}, K, K] weight expected, got {tuple(weight.shape)}")
+    return _ConvS2.apply(x, weight, bias, weight.detach().permute(2, 3, 1, 0).contiguous(), int(padding))
 
 
 def conv_block_tail(o1, o2, o3, res) -> torch.Tensor:
@@ -368,6 +450,12 @@ class _HGModule(nn.Module):
         conv = getattr(self, name)
         w = self._derived().get(name, (conv.weight,), lambda: conv.weight.detach().permute(2, 3, 1, 0).contiguous())
         return conv_s2(x, w, conv.bias, conv.kernel_size[0], conv.padding[0])
+
+    def _conv_s2_grad(self, x, name):
+        """``_conv_s2`` as a node of the graph (``_ConvS2``: data and weight gradients where they are needed)."""
+        conv = getattr(self, name)
+        w = self._derived().get(name, (conv.weight,), lambda: conv.weight.detach().permute(2, 3, 1, 0).contiguous())
+        return _ConvS2.apply(x, conv.weight, conv.bias, w, conv.padding[0])
 
 
 class ConvBlock(_HGModule):
@@ -473,8 +561,9 @@ class HourGlass(_HGModule):
 
 class HGFilter(_HGModule):
     def __init__(self, in_channel, feature_dim=256, num_hourglass=2, num_stack=4, norm="group", hg_down="ave_pool", *,
-                 trainable: bool = False):
+                 trainable: bool = False, stem_gradients: bool = False):
         super().__init__()
+        self.stem_gradients = bool(stem_gradients)     # (a plain attribute; consulted by the trainable forward only)
         self.in_channel = in_channel
         self.out_feature_dim = feature_dim
         self.num_hourglass = num_hourglass
@@ -525,20 +614,27 @@ class HGFilter(_HGModule):
 
     def _fwd_grad(self, x, rec):
         m = self._modules
-        with torch.no_grad():
-            x = self._conv_s2(x, "conv1")
-            if self.hg_down != "ave_pool":
-                x = self._norm(x, "bn1", True)
-                rec("stem", x)
-                x = self.conv2._fwd(x)
-                rec("conv2", x)
-                x = self._conv_s2(x, "down_conv2")
-        if self.hg_down == "ave_pool":
-            x = self._gn(x, ("bn1",))[0]
+        if self.stem_gradients:                        # the whole stem in the graph
+            x = self._gn(self._conv_s2_grad(x, "conv1"), ("bn1",))[0]
             rec("stem", x)
             x = self.conv2._fwd_grad(x)
             rec("conv2", x)
-            x = _AvgPool2x2.apply(x)
+            x = _AvgPool2x2.apply(x) if self.hg_down == "ave_pool" else self._conv_s2_grad(x, "down_conv2")
+        else:
+            with torch.no_grad():
+                x = self._conv_s2(x, "conv1")
+                if self.hg_down != "ave_pool":
+                    x = self._norm(x, "bn1", True)
+                    rec("stem", x)
+                    x = self.conv2._fwd(x)
+                    rec("conv2", x)
+                    x = self._conv_s2(x, "down_conv2")
+            if self.hg_down == "ave_pool":
+                x = self._gn(x, ("bn1",))[0]
+                rec("stem", x)
+                x = self.conv2._fwd_grad(x)
+                rec("conv2", x)
+                x = _AvgPool2x2.apply(x)
         x = self.conv3._fwd_grad(x)
         rec("conv3", x)
         x = self.conv4._fwd_grad(x)
@@ -558,8 +654,11 @@ class HGFilter(_HGModule):
         """``x`` [B, in_channel, H, W] -> [B, feature_dim, H / 4, W / 4] (channels_last memory).  ``trace``: a dict that receives
         ``stem``, ``conv2``, ``conv3``, ``conv4`` and per stack ``hg{i}``, ``ll{i}``, ``tmp_out{i}``."""
         if self._builds_graph("HGFilter"):
-            self._frozen_stem()
-            x = _plane(x, "HGFilter")                      # (detached: the image gets no gradient)
+            if self.stem_gradients:
+                x = _plane(x, "HGFilter", detach=False)    # (an image that requires a gradient gets one)
+            else:
+                self._frozen_stem()
+                x = _plane(x, "HGFilter")                  # (detached: the image gets no gradient)
             if x.shape[1] != self.in_channel:
                 raise ValueError(f"HGFilter: {self.in_channel} input channels expected, got {x.shape[1]}")
             low = 4 * 2 ** self.num_hourglass
