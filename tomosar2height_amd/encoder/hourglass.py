@@ -1,5 +1,4 @@
-"""HGFilter, the stacked-hourglass image encoder (reference: tomosar2height/encoder/hourglass.py:25-218), on the MI355X path: for
-inference by default, and with ``trainable=True`` (``norm='group'``) with gradients for everything behind the stem.
+"""HGFilter, the stacked-hourglass image encoder (reference: tomosar2height/encoder/hourglass.py:25-218), on the MI355X path.
 
 Constructor signatures, defaults, attribute names and ``state_dict`` keys and shapes are the reference's -- ``bn4`` is also
 ``downsample.0`` (both keys, one storage) and exists unused when ``in_planes == out_planes``; the ``add_module`` names are
@@ -7,36 +6,53 @@ Constructor signatures, defaults, attribute names and ``state_dict`` keys and sh
 ``al{i}``; an unknown ``hg_down`` raises ``NameError`` and ``norm='group'`` with ``hg_down='conv64'`` fails at construction as
 ``GroupNorm(32, 16)`` does -- so a reference checkpoint loads with ``strict=True``.
 
-Every layer runs on a t2h kernel over channels_last planes: the unbiased 3 x 3 convolutions on ``grid.conv3x3_fwd_``, every 1 x 1
-convolution on ``grid.conv1x1`` (``previous + ll + tmp_out_`` rides its addend epilogue), ``up1 + up2`` on the bicubic kernel's
-addend, and GroupNorm / folded BatchNorm, the stride-2 convolutions, the average pool and ``cat(out1, out2, out3) + residual``
-on csrc/hourglass.hip (include/t2h_hg.h, bound here: ``_lib.declare``).  ``bn1`` and ``bn4`` of a ConvBlock normalise the same
-tensor with the same groups: one statistics pass serves both.  The kernels have no NCHW form: an NCHW input is converted at the
-module boundary, whatever ``TomoSAR2Height.set_channels_last`` says, and the output is channels_last memory.
+Every layer runs on a t2h kernel over channels_last planes: the unbiased 3 x 3 convolutions on the kernels of ``grid.conv3x3_fwd_``,
+every 1 x 1 convolution on ``grid.conv1x1`` (``previous + ll + tmp_out_`` rides its addend epilogue), ``up1 + up2`` on the bicubic
+kernel's addend, and GroupNorm / folded BatchNorm, the stride-2 convolutions, the average pool and ``cat(out1, out2, out3) +
+residual`` on csrc/hourglass.hip (include/t2h_hg.h, bound here: ``_lib.declare``).  ``bn1`` and ``bn4`` of a ConvBlock normalise
+the same tensor with the same groups: one statistics pass serves both.  Layout: the kernels have no NCHW form, so an NCHW input is
+converted at the module boundary, whatever ``TomoSAR2Height.set_channels_last`` says, and the output is channels_last memory.  H
+and W of every plane must be powers of two (the 3 x 3 kernels), for ``HGFilter`` at least ``4 * 2 ** num_hourglass``: a
+``ValueError`` before any launch otherwise.
 
-Inference only by default (DESIGN.md sections 4.10 and 8).  The forward builds no autograd graph.  It raises
-``NotImplementedError`` when gradients are enabled and a parameter of the module requires one, and for ``norm='batch'`` under
-``train()`` (batch statistics); ``norm='group'`` computes the same thing in either mode.  H and W of every plane must be powers
-of two (the 3 x 3 kernels), for ``HGFilter`` at least ``4 * 2 ** num_hourglass``: a ``ValueError`` before any launch otherwise.
+Each module states its layer sequence once (``_fwd``), in terms of a small set of operations -- norm + ReLU for one or two affine
+pairs with an optional pass-through of the input, 3 x 3 convolution, stride-2 convolution, pool, tail, upsample-add -- and runs it
+on one of two implementations of that set: ``_Plain``, the kernel wrappers of this file under ``torch.no_grad()``, or ``_Graph``,
+the autograd ``Function`` s over the same wrappers (``_GroupNorm``, ``grid._Conv3x3``, ``_ConvS2``, ``_AvgPool2x2``, ``_BlockTail``,
+``_Upsample2xAdd``; ``grid.conv1x1`` serves both).  Both launch the same kernels on the same operands: the outputs are equal bit
+for bit.
 
-Training is opt-in: ``ConvBlock``, ``HourGlass`` and ``HGFilter`` take a keyword-only ``trainable=False`` (a plain attribute, no
-parameter or buffer; setting it on a module sets it on the hourglass modules below it).  With ``trainable=True``, ``norm='group'``
-and gradients enabled the forward builds an autograd graph of ``_GroupNorm`` (GroupNorm [+ ReLU], ``t2h_hg_groupnorm_bwd_*``),
-``grid._Conv3x3``, ``grid.conv1x1`` with its addend, ``_AvgPool2x2``, ``_BlockTail`` and ``_Upsample2xAdd``; gradients reach every
-parameter and the input, in ``train()`` and ``eval()`` alike.  A tensor with two consumers inside a block (the block's input:
-bn1, bn4 and the identity residual; out1 and out2: the next norm and the tail) gets the sum of their gradients in the GroupNorm
-backward's addend, not in a pass of its own.  Under ``torch.no_grad()`` the inference path runs unchanged.  Not built, refused
-before any launch: ``norm='batch'`` with ``trainable=True`` in either mode; for ``HGFilter`` a stem that requires a gradient --
-``conv1``, and ``down_conv2`` of ``hg_down='conv64' / 'conv128'``, so the image gets none either; and ``Trainer`` refuses a model
-whose image encoder is trainable.
+By default the modules run for inference (DESIGN.md sections 4.10 and 8): ``_Plain`` throughout, no autograd graph.  The forward
+raises ``NotImplementedError`` when gradients are enabled and a parameter of the module requires one, and for ``norm='batch'``
+under ``train()`` (batch statistics); ``norm='batch'`` in ``eval()`` runs on scale and shift folded from the running statistics,
+``norm='group'`` computes the same thing in either mode.
 
-The stem trains behind a second keyword-only switch of ``HGFilter``, ``stem_gradients=False`` (a plain attribute too; read by the
-trainable forward only, so it can ride ``model.encoder2_kwargs``).  With ``trainable=True, stem_gradients=True`` the stem is part
-of the graph: ``conv1`` and ``down_conv2`` run through ``_ConvS2`` (``t2h_hg_conv_s2_dgrad`` / ``_wgrad``: the data gradient
-only for an input that needs one, the weight gradient only for a weight or bias that does), ``bn1`` through ``_GroupNorm``,
-``conv2`` through its own graph, and an image with ``requires_grad`` gets ``.grad``.  Switched off, every path and message above
-is unchanged.  ``conv2d_stride2`` is the differentiable stride-2 convolution on its own.
+Two keyword-only switches, both plain attributes (no parameter, no buffer, nothing in the ``state_dict``), add training:
+
+* ``trainable=False`` on ``ConvBlock``, ``HourGlass`` and ``HGFilter``; setting it on a module sets it on the hourglass modules
+  below it.  With ``trainable=True``, ``norm='group'`` and gradients enabled the forward runs on ``_Graph``: gradients reach every
+  parameter behind the stem and, for ``ConvBlock`` and ``HourGlass``, the input, in ``train()`` and ``eval()`` alike.  Under
+  ``torch.no_grad()`` the forward is the inference one.  ``HGFilter`` keeps its stem out of the graph: ``conv1`` -- and, for
+  ``hg_down='conv64' / 'conv128'``, everything up to ``down_conv2``, since what lies in front of a stride-2 convolution would need
+  its data gradient -- runs on ``_Plain`` and the image gets no gradient.
+* ``stem_gradients=False`` on ``HGFilter``, read by the trainable forward only (so it can ride ``model.encoder2_kwargs``).  With
+  ``trainable=True, stem_gradients=True`` the whole stem runs on ``_Graph``: ``conv1`` and ``down_conv2`` through ``_ConvS2``
+  (``t2h_hg_conv_s2_dgrad`` / ``_wgrad``: the data gradient only for an input that needs one, the weight gradient only for a
+  weight or bias that does), and an image with ``requires_grad`` gets ``.grad``.
+
+Refused before any launch, in this order on the trainable path: ``norm='batch'`` with ``trainable=True``, in either mode and with
+gradients enabled or not; without ``stem_gradients``, a stem layer named above that requires a gradient; then what every forward
+checks -- device, dtype and rank of the input, the channel count, the plane size.  ``Trainer`` refuses a model whose image
+encoder is trainable.
+
+A tensor with two consumers inside a block (the block's input: bn1, bn4 and the identity residual; out1 and out2: the next norm
+and the tail) is handed to the second one by the norm operation's pass-through -- the tensor itself on ``_Plain``, an alias out
+of the ``_GroupNorm`` node on ``_Graph``, whose backward takes that consumer's gradient, and each affine pair's dx, as the addend
+of the next apply: the tensor gets the sum of its gradients without a pass that only adds.
+
+``group_norm``, ``avg_pool2x2``, ``conv2d_stride2`` and ``conv_block_tail`` are the differentiable operations on their own.
 """
+import contextlib
 import ctypes
 
 import torch
@@ -375,6 +391,58 @@ def _check_planes(x, what, min_h, min_w):
                          "take power-of-two planes)")
 
 
+def _weight_cl(conv):
+    if not conv.weight.permute(0, 2, 3, 1).is_contiguous():          # the kernels read [Cout][3][3][Cin]: re-laid once, in place
+        conv.weight.data = conv.weight.data.contiguous(memory_format=torch.channels_last)
+    return conv.weight
+
+
+class _Plain:
+    """The operations of the forward bodies on the kernel wrappers, without a graph (a namespace, never instantiated: plain
+    functions); ``scope``: what a region of a forward that runs on this set is wrapped in."""
+    scope = torch.no_grad
+    pool, tail, up_add = avgpool2x2, block_tail, upsample2x_bicubic_add
+
+    def norm(module, x, names, thru=False):
+        """(relu(layer(x)) for the GroupNorm / eval-mode BatchNorm2d attributes ``names`` -- one, or two over the same statistics
+        --, then, ``thru``, ``x`` again for another consumer of it)."""
+        layers = [getattr(module, n) for n in names]
+        if isinstance(layers[0], nn.GroupNorm):
+            stats = group_norm_stats(x, layers[0].num_groups, layers[0].eps)
+            ys = tuple(norm_apply(x, stats, layer.weight, layer.bias, layer.num_groups, True) for layer in layers)
+        else:
+            ys = tuple(norm_apply(x, None, *module._folded(n), 1, True) for n in names)
+        return ys + ((x,) if thru else ())
+
+    def conv3x3(x, conv):
+        w = _weight_cl(conv)
+        b, _, h, wd = x.shape
+        return grid.conv3x3_fwd_(x, w, conv.bias, grid._empty_cl(b, w.shape[0], h, wd, x.device))
+
+    def stride2(x, conv, w_kkio):
+        return conv_s2(x, w_kkio, conv.bias, conv.kernel_size[0], conv.padding[0])
+
+
+class _Graph:
+    """The same operations as nodes of an autograd graph (``norm='group'``); ``thru`` is the alias the ``_GroupNorm`` returns."""
+    scope = contextlib.nullcontext
+    pool, tail, up_add = _AvgPool2x2.apply, _BlockTail.apply, _Upsample2xAdd.apply
+
+    def norm(module, x, names, thru=False):
+        layers = [getattr(module, n) for n in names]
+        affine = [p for layer in layers for p in (layer.weight, layer.bias)]
+        return _GroupNorm.apply(x, layers[0].num_groups, layers[0].eps, True, thru, *affine)
+
+    def conv3x3(x, conv):
+        _weight_cl(conv)
+        if not grid.conv3x3_supported(x, conv):
+            raise NotImplementedError(f"no 3 x 3 kernel for {conv.in_channels} -> {conv.out_channels} channels on a {tuple(x.shape[2:])} plane")
+        return grid._Conv3x3.apply(x, conv.weight, conv.bias, False, False, False)
+
+    def stride2(x, conv, w_kkio):
+        return _ConvS2.apply(x, conv.weight, conv.bias, w_kkio, conv.padding[0])
+
+
 class _HGModule(nn.Module):
     @property
     def trainable(self) -> bool:
@@ -398,23 +466,14 @@ class _HGModule(nn.Module):
                                       "frozen-BatchNorm backward nor batch statistics (norm='group' trains)")
         return torch.is_grad_enabled()
 
-    def _gn(self, x, names, thru=False):
-        """``_GroupNorm`` + ReLU of ``x`` for the GroupNorm attributes ``names`` (one, or two over the same statistics)."""
-        layers = [getattr(self, n) for n in names]
-        affine = [p for layer in layers for p in (layer.weight, layer.bias)]
-        return _GroupNorm.apply(x, layers[0].num_groups, layers[0].eps, True, thru, *affine)
-
-    def _conv3x3_grad(self, x, conv):
-        self._weight_cl(conv)
-        if not grid.conv3x3_supported(x, conv):
-            raise NotImplementedError(f"no 3 x 3 kernel for {conv.in_channels} -> {conv.out_channels} channels on a {tuple(x.shape[2:])} plane")
-        return grid._Conv3x3.apply(x, conv.weight, conv.bias, False, False, False)
-
-    @staticmethod
-    def _weight_cl(conv):
-        if not conv.weight.permute(0, 2, 3, 1).is_contiguous():          # the kernels read [Cout][3][3][Cin]: re-laid once, in place
-            conv.weight.data = conv.weight.data.contiguous(memory_format=torch.channels_last)
-        return conv.weight
+    def _begin(self, x, what: str, low: int):
+        """What a forward starts with: (the operation set of this call, ``x`` as a checked plane of at least ``low`` x ``low``)."""
+        graph = self._builds_graph(what)
+        if not graph:
+            _require_inference(self, what)
+        x = _plane(x, what, detach=not graph)
+        _check_planes(x, what, low, low)
+        return (_Graph if graph else _Plain), x
 
     def _derived(self) -> _lib.Derived:
         d = self.__dict__.get("_hg_derived")
@@ -422,14 +481,9 @@ class _HGModule(nn.Module):
             d = self.__dict__["_hg_derived"] = _lib.Derived()
         return d
 
-    def _norm(self, x, name, relu, stats=None):
-        """relu?(layer(x)) for the GroupNorm / eval-mode BatchNorm2d attribute ``name``; ``stats``: GroupNorm statistics of ``x``
-        already at hand."""
+    def _folded(self, name):
+        """(scale, shift) of the eval-mode BatchNorm2d attribute ``name``, cached per version of its tensors."""
         layer = getattr(self, name)
-        if isinstance(layer, nn.GroupNorm):
-            if stats is None:
-                stats = group_norm_stats(x, layer.num_groups, layer.eps)
-            return norm_apply(x, stats, layer.weight, layer.bias, layer.num_groups, relu)
         if layer.training:
             raise NotImplementedError("BatchNorm2d batch statistics are not built: norm='batch' runs in eval() only")
 
@@ -437,25 +491,13 @@ class _HGModule(nn.Module):
             s = layer.weight.double() / torch.sqrt(layer.running_var.double() + layer.eps)
             return (s.float().contiguous(), (layer.bias.double() - layer.running_mean.double() * s).float().contiguous())
 
-        scale, shift = self._derived().get(name, (layer.weight, layer.bias, layer.running_mean, layer.running_var), fold)
-        return norm_apply(x, None, scale, shift, 1, relu)
+        return self._derived().get(name, (layer.weight, layer.bias, layer.running_mean, layer.running_var), fold)
 
-    def _conv3x3(self, x, conv):
-        w = self._weight_cl(conv)
-        b, _, h, wd = x.shape
-        y = grid._empty_cl(b, w.shape[0], h, wd, x.device)
-        return grid.conv3x3_fwd_(x, w, conv.bias, y)
-
-    def _conv_s2(self, x, name):
+    def _conv_s2(self, ops, x, name):
+        """The stride-2 convolution attribute ``name`` on its weight re-laid to [K, K, Cin, Cout], cached per weight version."""
         conv = getattr(self, name)
         w = self._derived().get(name, (conv.weight,), lambda: conv.weight.detach().permute(2, 3, 1, 0).contiguous())
-        return conv_s2(x, w, conv.bias, conv.kernel_size[0], conv.padding[0])
-
-    def _conv_s2_grad(self, x, name):
-        """``_conv_s2`` as a node of the graph (``_ConvS2``: data and weight gradients where they are needed)."""
-        conv = getattr(self, name)
-        w = self._derived().get(name, (conv.weight,), lambda: conv.weight.detach().permute(2, 3, 1, 0).contiguous())
-        return _ConvS2.apply(x, conv.weight, conv.bias, w, conv.padding[0])
+        return ops.stride2(x, conv, w)
 
 
 class ConvBlock(_HGModule):
@@ -480,41 +522,24 @@ class ConvBlock(_HGModule):
         else:
             self.downsample = None
 
-    def _fwd(self, x):
-        stats = group_norm_stats(x, self.bn1.num_groups, self.bn1.eps) if isinstance(self.bn1, nn.GroupNorm) else None
-        out1 = self._conv3x3(self._norm(x, "bn1", True, stats), self.conv1)
-        out2 = self._conv3x3(self._norm(out1, "bn2", True), self.conv2)
-        out3 = self._conv3x3(self._norm(out2, "bn3", True), self.conv3)
-        residual = x
+    def _fwd(self, ops, x):
+        """``x``, ``out1`` and ``out2`` each have two consumers: the second one takes the norm's pass-through."""
         if self.downsample is not None:
-            residual = grid.conv1x1(self._norm(x, "bn4", True, stats), self.downsample[2])
-        return block_tail(out1, out2, out3, residual)
-
-    def _fwd_grad(self, x):
-        """``_fwd`` as an autograd graph (``norm='group'``).  ``x``, ``out1`` and ``out2`` each have two consumers: the second one
-        takes the alias the ``_GroupNorm`` returns, whose gradient that backward adds in its own pass."""
-        if self.downsample is not None:
-            y1, y4 = self._gn(x, ("bn1", "bn4"))
+            y1, y4 = ops.norm(self, x, ("bn1", "bn4"))
             residual = grid.conv1x1(y4, self.downsample[2])
         else:
-            y1, residual = self._gn(x, ("bn1",), thru=True)
-        out1 = self._conv3x3_grad(y1, self.conv1)
-        y2, out1 = self._gn(out1, ("bn2",), thru=True)
-        out2 = self._conv3x3_grad(y2, self.conv2)
-        y3, out2 = self._gn(out2, ("bn3",), thru=True)
-        out3 = self._conv3x3_grad(y3, self.conv3)
-        return _BlockTail.apply(out1, out2, out3, residual)
+            y1, residual = ops.norm(self, x, ("bn1",), thru=True)
+        out1 = ops.conv3x3(y1, self.conv1)
+        y2, out1 = ops.norm(self, out1, ("bn2",), thru=True)
+        out2 = ops.conv3x3(y2, self.conv2)
+        y3, out2 = ops.norm(self, out2, ("bn3",), thru=True)
+        out3 = ops.conv3x3(y3, self.conv3)
+        return ops.tail(out1, out2, out3, residual)
 
     def forward(self, x):
-        if self._builds_graph("ConvBlock"):
-            x = _plane(x, "ConvBlock", detach=False)
-            _check_planes(x, "ConvBlock", 1, 1)
-            return self._fwd_grad(x)
-        _require_inference(self, "ConvBlock")
-        x = _plane(x, "ConvBlock")
-        _check_planes(x, "ConvBlock", 1, 1)
-        with torch.no_grad():
-            return self._fwd(x)
+        ops, x = self._begin(x, "ConvBlock", 1)
+        with ops.scope():
+            return self._fwd(ops, x)
 
 
 class HourGlass(_HGModule):
@@ -533,30 +558,17 @@ class HourGlass(_HGModule):
             self.add_module("b2_plus_" + str(level), ConvBlock(self.features, self.features, norm=self.norm))
         self.add_module("b3_" + str(level), ConvBlock(self.features, self.features, norm=self.norm))
 
-    def _fwd(self, level, inp):
-        up1 = self._modules["b1_" + str(level)]._fwd(inp)
-        low1 = self._modules["b2_" + str(level)]._fwd(avgpool2x2(inp))
-        low2 = self._fwd(level - 1, low1) if level > 1 else self._modules["b2_plus_" + str(level)]._fwd(low1)
-        low3 = self._modules["b3_" + str(level)]._fwd(low2)
-        return upsample2x_bicubic_add(low3, up1)
-
-    def _fwd_grad(self, level, inp):
-        up1 = self._modules["b1_" + str(level)]._fwd_grad(inp)
-        low1 = self._modules["b2_" + str(level)]._fwd_grad(_AvgPool2x2.apply(inp))
-        low2 = self._fwd_grad(level - 1, low1) if level > 1 else self._modules["b2_plus_" + str(level)]._fwd_grad(low1)
-        low3 = self._modules["b3_" + str(level)]._fwd_grad(low2)
-        return _Upsample2xAdd.apply(low3, up1)
+    def _fwd(self, ops, level, inp):
+        up1 = self._modules["b1_" + str(level)]._fwd(ops, inp)
+        low1 = self._modules["b2_" + str(level)]._fwd(ops, ops.pool(inp))
+        low2 = self._fwd(ops, level - 1, low1) if level > 1 else self._modules["b2_plus_" + str(level)]._fwd(ops, low1)
+        low3 = self._modules["b3_" + str(level)]._fwd(ops, low2)
+        return ops.up_add(low3, up1)
 
     def forward(self, x):
-        if self._builds_graph("HourGlass"):
-            x = _plane(x, "HourGlass", detach=False)
-            _check_planes(x, "HourGlass", 2 ** self.depth, 2 ** self.depth)
-            return self._fwd_grad(self.depth, x)
-        _require_inference(self, "HourGlass")
-        x = _plane(x, "HourGlass")
-        _check_planes(x, "HourGlass", 2 ** self.depth, 2 ** self.depth)
-        with torch.no_grad():
-            return self._fwd(self.depth, x)
+        ops, x = self._begin(x, "HourGlass", 2 ** self.depth)
+        with ops.scope():
+            return self._fwd(ops, self.depth, x)
 
 
 class HGFilter(_HGModule):
@@ -612,83 +624,46 @@ class HGFilter(_HGModule):
                                       + ("" if self.hg_down == "ave_pool" else ", down_conv2 and what lies in front of it")
                                       + "); call requires_grad_(False) on them")
 
-    def _fwd_grad(self, x, rec):
-        m = self._modules
-        if self.stem_gradients:                        # the whole stem in the graph
-            x = self._gn(self._conv_s2_grad(x, "conv1"), ("bn1",))[0]
-            rec("stem", x)
-            x = self.conv2._fwd_grad(x)
-            rec("conv2", x)
-            x = _AvgPool2x2.apply(x) if self.hg_down == "ave_pool" else self._conv_s2_grad(x, "down_conv2")
-        else:
-            with torch.no_grad():
-                x = self._conv_s2(x, "conv1")
-                if self.hg_down != "ave_pool":
-                    x = self._norm(x, "bn1", True)
-                    rec("stem", x)
-                    x = self.conv2._fwd(x)
-                    rec("conv2", x)
-                    x = self._conv_s2(x, "down_conv2")
-            if self.hg_down == "ave_pool":
-                x = self._gn(x, ("bn1",))[0]
-                rec("stem", x)
-                x = self.conv2._fwd_grad(x)
-                rec("conv2", x)
-                x = _AvgPool2x2.apply(x)
-        x = self.conv3._fwd_grad(x)
-        rec("conv3", x)
-        x = self.conv4._fwd_grad(x)
-        rec("conv4", x)
-        previous, tmp_out = x, None
-        for i in range(self.num_modules):
-            hg = m["m" + str(i)]._fwd_grad(self.num_hourglass, previous)
-            ll = m["top_m_" + str(i)]._fwd_grad(hg)
-            ll = self._gn(grid.conv1x1(ll, m["conv_last" + str(i)]), ("bn_end" + str(i),))[0]
-            tmp_out = grid.conv1x1(ll, m["l" + str(i)])
-            rec(f"hg{i}", hg), rec(f"ll{i}", ll), rec(f"tmp_out{i}", tmp_out)
-            if i < self.num_modules - 1:
-                previous = grid.conv1x1(tmp_out, m["al" + str(i)], grid.conv1x1(ll, m["bl" + str(i)], previous))
-        return tmp_out
-
     def forward(self, x, trace: dict = None):
         """``x`` [B, in_channel, H, W] -> [B, feature_dim, H / 4, W / 4] (channels_last memory).  ``trace``: a dict that receives
         ``stem``, ``conv2``, ``conv3``, ``conv4`` and per stack ``hg{i}``, ``ll{i}``, ``tmp_out{i}``."""
-        if self._builds_graph("HGFilter"):
-            if self.stem_gradients:
-                x = _plane(x, "HGFilter", detach=False)    # (an image that requires a gradient gets one)
-            else:
-                self._frozen_stem()
-                x = _plane(x, "HGFilter")                  # (detached: the image gets no gradient)
-            if x.shape[1] != self.in_channel:
-                raise ValueError(f"HGFilter: {self.in_channel} input channels expected, got {x.shape[1]}")
-            low = 4 * 2 ** self.num_hourglass
-            _check_planes(x, "HGFilter", low, low)
-            return self._fwd_grad(x, (lambda k, v: trace.__setitem__(k, v)) if trace is not None else (lambda k, v: None))
-        _require_inference(self, "HGFilter")
-        x = _plane(x, "HGFilter")
+        graph = self._builds_graph("HGFilter")
+        if not graph:
+            _require_inference(self, "HGFilter")
+        elif not self.stem_gradients:
+            self._frozen_stem()
+        x = _plane(x, "HGFilter", detach=not (graph and self.stem_gradients))      # (with the stem in the graph the image gets .grad)
         if x.shape[1] != self.in_channel:
             raise ValueError(f"HGFilter: {self.in_channel} input channels expected, got {x.shape[1]}")
         low = 4 * 2 ** self.num_hourglass
         _check_planes(x, "HGFilter", low, low)
         if self.hg_down not in ("ave_pool", "conv64", "conv128"):
             raise NameError("Unknown HGFilter downsampling method!")
-        rec = (lambda k, v: trace.__setitem__(k, v)) if trace is not None else (lambda k, v: None)
-        with torch.no_grad():
-            x = self._norm(self._conv_s2(x, "conv1"), "bn1", True)
-            rec("stem", x)
-            x = self.conv2._fwd(x)
-            rec("conv2", x)
-            x = avgpool2x2(x) if self.hg_down == "ave_pool" else self._conv_s2(x, "down_conv2")
-            x = self.conv3._fwd(x)
+        # the operation set per region: ``conv1``; ``bn1`` .. the pool / ``down_conv2``; everything behind.  A frozen stem stays
+        # without a graph up to its last stride-2 convolution
+        rest = _Graph if graph else _Plain
+        head = rest if self.stem_gradients else _Plain
+        front = rest if self.stem_gradients or self.hg_down == "ave_pool" else _Plain
+        rec = trace.__setitem__ if trace is not None else (lambda k, v: None)
+        m = self._modules
+        with rest.scope():
+            with head.scope():
+                x = self._conv_s2(head, x, "conv1")
+            with front.scope():
+                x = front.norm(self, x, ("bn1",))[0]
+                rec("stem", x)
+                x = self.conv2._fwd(front, x)
+                rec("conv2", x)
+                x = front.pool(x) if self.hg_down == "ave_pool" else self._conv_s2(front, x, "down_conv2")
+            x = self.conv3._fwd(rest, x)
             rec("conv3", x)
-            x = self.conv4._fwd(x)
+            x = self.conv4._fwd(rest, x)
             rec("conv4", x)
             previous, tmp_out = x, None
             for i in range(self.num_modules):
-                m = self._modules
-                hg = m["m" + str(i)]._fwd(self.num_hourglass, previous)
-                ll = m["top_m_" + str(i)]._fwd(hg)
-                ll = self._norm(grid.conv1x1(ll, m["conv_last" + str(i)]), "bn_end" + str(i), True)
+                hg = m["m" + str(i)]._fwd(rest, self.num_hourglass, previous)
+                ll = m["top_m_" + str(i)]._fwd(rest, hg)
+                ll = rest.norm(self, grid.conv1x1(ll, m["conv_last" + str(i)]), ("bn_end" + str(i),))[0]
                 tmp_out = grid.conv1x1(ll, m["l" + str(i)])
                 rec(f"hg{i}", hg), rec(f"ll{i}", ll), rec(f"tmp_out{i}", tmp_out)
                 if i < self.num_modules - 1:

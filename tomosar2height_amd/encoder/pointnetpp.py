@@ -67,36 +67,27 @@ class _FoldedLayers(nn.Module):
     def wants_batch_stats(self) -> bool:
         return self.training and self.batch_statistics
 
-    def folded(self):
+    def folded(self, graph=False):
+        """[(W', b')] of the layers.  By default without a graph, cached; ``graph``: the same float64 torch operations under
+        autograd, uncached -- the same bytes, with the chain rule to ``conv.weight``, ``conv.bias``, ``bn.weight`` and ``bn.bias``
+        (the running statistics are constants)."""
         pairs = list(zip(self.mlp_convs, self.mlp_bns))
 
         def fold():
             layers = []
             for conv, bn in pairs:
                 _lib.require_device(conv.weight, what="PointNetPlusPlus layer")
-                s = bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps)
+                s = bn.weight.double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
                 w = conv.weight.reshape(conv.weight.shape[0], -1).double() * s[:, None]
-                b = (conv.bias.double() - bn.running_mean.double()) * s + bn.bias.double()
-                wp = torch.zeros(w.shape[0], _pad4(w.shape[1]), dtype=torch.float32, device=w.device)
-                wp[:, :w.shape[1]] = w
-                layers.append((wp, b.float().contiguous()))
+                b = (conv.bias.double() - bn.running_mean.detach().double()) * s + bn.bias.double()
+                k = w.shape[1]
+                layers.append((torch.nn.functional.pad(w.float(), (0, _pad4(k) - k)), b.float()))
             return layers
 
+        if graph:
+            return fold()
         sources = [t for conv, bn in pairs for t in (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)]
-        return self.__dict__["_fold"].get("layers", sources, fold)
-
-    def folded_graph(self):
-        """The fold as float64 torch operations under autograd, rounded once: the same bytes as ``folded()``, with the chain
-        rule to ``conv.weight``, ``conv.bias``, ``bn.weight`` and ``bn.bias`` (the running statistics are constants)."""
-        layers = []
-        for conv, bn in zip(self.mlp_convs, self.mlp_bns):
-            _lib.require_device(conv.weight, what="PointNetPlusPlus layer")
-            s = bn.weight.double() / torch.sqrt(bn.running_var.detach().double() + bn.eps)
-            w = conv.weight.reshape(conv.weight.shape[0], -1).double() * s[:, None]
-            b = (conv.bias.double() - bn.running_mean.detach().double()) * s + bn.bias.double()
-            k = w.shape[1]
-            layers.append((torch.nn.functional.pad(w.float(), (0, _pad4(k) - k)), b.float()))
-        return layers
+        return self.__dict__["_fold"].get("layers", sources, fold)          # (``Derived.get`` fills under ``no_grad``)
 
     def wants_graph(self, *features) -> bool:
         """True when this stage has to build an autograd graph: gradients are enabled and a parameter of its layers, or a
@@ -117,7 +108,7 @@ class _FoldedLayers(nn.Module):
         if self.wants_batch_stats():
             return self._chain_batch_stats(rows, nsample)
         if graph:
-            return _Chain.apply(rows, nsample, *[t for wb in self.folded_graph() for t in wb])
+            return _Chain.apply(rows, nsample, *[t for wb in self.folded(graph=True) for t in wb])
         with torch.no_grad():
             for w, b in self.folded():
                 y = torch.empty(rows.shape[0], w.shape[0], dtype=torch.float32, device=rows.device)
