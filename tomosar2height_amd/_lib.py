@@ -16,9 +16,10 @@ import os
 
 import torch  # noqa: F401  (must precede the CDLL below, see docstring)
 
+from . import switches
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# T2H_LIBRARY: load another build of the same ABI (A/B runs of a kernel change; a site-specific install path)
-LIB_PATH = os.environ.get("T2H_LIBRARY") or os.path.join(_HERE, "libt2h_hip.so")
+LIB_PATH = switches.get("T2H_LIBRARY") or os.path.join(_HERE, "libt2h_hip.so")
 ABI_VERSION = 20
 
 _vp, _i, _i64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t
@@ -238,7 +239,7 @@ class T2HLibraryError(RuntimeError):
 # decoder, convolutions other than 3x3/s1/p1, 1x1 and 2x2/s2-transposed, the NCHW grid side).  They used to run on
 # MIOpen / rocBLAS / ATen silently; now such a call RAISES unless fallbacks are allowed, and every fallback taken is
 # counted, so a regression that flips a layer of the default path onto a vendor library cannot pass the tests.
-_fallback_allowed = os.environ.get("T2H_ALLOW_LIBRARY_FALLBACK", "0") == "1"
+_fallback_allowed = switches.get("T2H_ALLOW_LIBRARY_FALLBACK")
 _fallback_counts = {}
 
 
@@ -383,8 +384,7 @@ def _entry(name: str):
     return getattr(load(), name)
 
 
-# test instrumentation: NaN patterns into every free CU's LDS before every entry point (t2h_debug_poison_lds, include/t2h.h)
-_POISON_LDS = os.environ.get("T2H_POISON_LDS", "0") == "1"
+_POISON_LDS = switches.get("T2H_POISON_LDS")
 
 
 def call(name: str, *args, nbytes: int = 0, flops: int = 0, tag: str = None):
@@ -487,7 +487,7 @@ def stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
-_CACHE_READY = os.environ.get("T2H_CACHE_READY", "1") != "0"      # 0: the r04-r06 behaviour, to show that the tests catch it
+_CACHE_READY = switches.get("T2H_CACHE_READY")
 
 
 class Ready:

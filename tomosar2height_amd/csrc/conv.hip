@@ -410,8 +410,8 @@ RowsPlan rows_plan(long long M, int N, int K) {
     int splits = 1;
     // fewer tiles than two per CU: split the reduction.  ~512 workgroups for planes from 256 x 256 up (768 / 1024 there:
     // +10-30 % slower), ~768 for the smaller ones (128->128 at 128^2: 65 -> 60 us; 256 / 384: slower)
-    static const long long tgt_small = getenv("T2H_CONV_ROWS_WGS_SMALL") ? atoll(getenv("T2H_CONV_ROWS_WGS_SMALL")) : 768;
-    static const long long tgt_large = getenv("T2H_CONV_ROWS_WGS_LARGE") ? atoll(getenv("T2H_CONV_ROWS_WGS_LARGE")) : 512;
+    static const long long tgt_small = env_ll("T2H_CONV_ROWS_WGS_SMALL", 768);
+    static const long long tgt_large = env_ll("T2H_CONV_ROWS_WGS_LARGE", 512);
     const long long tgt = M <= 16384 ? tgt_small : tgt_large;
     if (tiles < tgt) {
         splits = (int)((tgt + tiles - 1) / tiles);
@@ -457,7 +457,7 @@ RowsPlan rows_plan_for(long long M, int Cin, int Cout) {
         // 512 -> 256 channels is a 1024 x 1024 x 512 GEMM: 64 tiles of 128 x 128 would occupy a quarter of the CUs)
         r.splits = 1; r.k_chunk = sh.K;
         const long long row_tiles = (M + 127) / 128;
-        static const long long up_tiles = getenv("T2H_UPCONV_FWD_TILES") ? atoll(getenv("T2H_UPCONV_FWD_TILES")) : 256;
+        static const long long up_tiles = env_ll("T2H_UPCONV_FWD_TILES", 256);
         while (r.bn > 32 && row_tiles * ((sh.N + r.bn - 1) / r.bn) < up_tiles) r.bn >>= 1;
     }
     return r;
@@ -512,7 +512,7 @@ WgradPlan wgrad_plan_for(long long P, int rows, int ncols) {
     // 70 -> 61 us, 256->256 at 64^2: 70 -> 63) -- half the slabs to write and reduce, twice the main loop per epilogue;
     // from 256 x 256 up 1024 stays (512: +4-9 % slower there; 2048 wins or loses by shape within +-5 %)
     // (T2H_CONV_WGRAD_WGS: the A/B of DESIGN.md section 4 -- fewer workgroups = fewer split slabs = less traffic, more time)
-    static const long long forced = getenv("T2H_CONV_WGRAD_WGS") ? atoll(getenv("T2H_CONV_WGRAD_WGS")) : 0;
+    static const long long forced = env_ll("T2H_CONV_WGRAD_WGS", 0);
     const long long target = forced > 0 ? forced : (P <= 16384 ? 512 : 1024);
     long long want = target / tiles;       // <= 1024 workgroups = one resident wave; 1025 would leave one running alone
                                          // (measured: 64->128 at 512^2, 5 tiles: 464 us with 1025 workgroups, 390 with 1020)

@@ -962,20 +962,20 @@ RowsPlan bx3_rows_plan(int B, int H, int W, int Kc, int Nc, int ntap = 9, int up
     }
     // 8-row tiles where they still give every CU its two workgroups twice over (512 x 512 planes: 1024 tiles); measured on
     // 64->128 / 128->64 / 64->32 at 512^2: 203 -> 185, 239 -> 194, 76 -> 72 us, and slower at 256^2 (256 tiles: one per CU)
-    static const long long min_tiles8 = getenv("T2H_BX3_TILES8") ? atoll(getenv("T2H_BX3_TILES8")) : 1024;
+    static const long long min_tiles8 = env_ll("T2H_BX3_TILES8", 1024);
     const long long tiles8 = H % 8 == 0 ? (long long)B * (H / 8) * (W / TW) * (Nc / r.bn) : 0;
     r.tall = tiles8 >= min_tiles8 && !(ntap == 1 && r.bn == 128);        // (1-tap, 128 columns: the 8-row images would not fit twice per CU)
     r.tiles = r.tall ? tiles8 : (long long)B * (H / 4) * (W / TW) * (Nc / r.bn);
     // few tiles (small planes) and a short reduction (<= 128 channels: few chunks to split): 64-column tiles double the tile count
     // instead of splitting the reduction into slabs (64->128 at 128^2: 32 -> 24 us, 128->256 at 64^2: 31 -> 29; with longer
     // reductions the narrower tiles lose: 512->256 at 64^2 dgrad 64 -> 98 us).  T2H_BX3_NARROW=0: A/B
-    static const bool narrow = !(getenv("T2H_BX3_NARROW") && getenv("T2H_BX3_NARROW")[0] == '0');
+    static const bool narrow = env_flag("T2H_BX3_NARROW", true);
     if (narrow && !r.tall && r.bn == 128 && r.tiles < 256 && Kc <= 128) { r.bn = 64; r.tiles *= 2; }
     // small planes with many channels: fewer tiles than the chip holds workgroups -> split the reduction over whole 32-channel
     // chunks into slabs (summed in a fixed order by reduce_rows_epilogue, which also applies the epilogue): deterministic
     r.splits = 1;
     const int nchunk = ntap == 9 ? Kc / (r.tall ? 16 : 32) : Kc / (r.tall ? 32 : 64);      // (the 1-tap form stages 64 / 32 channels)
-    static const long long target = getenv("T2H_BX3_ROWS_WGS") ? atoll(getenv("T2H_BX3_ROWS_WGS")) : 512;
+    static const long long target = env_ll("T2H_BX3_ROWS_WGS", 512);
     if (!r.tall && r.tiles < target / 2) {
         long long want = (target + r.tiles - 1) / r.tiles;
         if (want > nchunk) want = nchunk;
@@ -1019,7 +1019,7 @@ int npl_of(int flags) { return (flags & T2H_F16X2) ? 2 : ((flags & T2H_BF16) ? 1
 const float *f16_trailer(const void *wf, size_t planes_bytes) { return reinterpret_cast<const float *>(static_cast<const unsigned char *>(wf) + planes_bytes); }
 
 bool persist_n_enabled() {
-    static const bool on = !(getenv("T2H_BX3_PERSIST_N") && getenv("T2H_BX3_PERSIST_N")[0] == '0');
+    static const bool on = env_flag("T2H_BX3_PERSIST_N", true);
     return on;
 }
 
@@ -1060,11 +1060,11 @@ int launch_rows(RowsArgs a, int npl, void *ws, size_t ws_bytes, hipStream_t s, c
         const long long row_tiles = (long long)a.B * (a.H / 4) * (a.W / TW);
         const int pbn = r.bn == 128 ? 64 : r.bn;                          // (128-column tiles spill in this form)
         const int ntn = a.Nc / pbn;
-        static const long long persist_wgs = getenv("T2H_BX3_PERSIST_WGS") ? atoll(getenv("T2H_BX3_PERSIST_WGS")) : 2048;
+        static const long long persist_wgs = env_ll("T2H_BX3_PERSIST_WGS", 2048);
         // r06: at least four column groups however many row tiles there are -- with four tiles per launch (2 048 row tiles) a
         // single group made every workgroup walk all 43 column tiles: 289 us per tile against 181 with four groups and the 185 of
         // one tile per launch (profiles/level256_probe.py; T2H_BX3_PERSIST_MIN_GROUPS)
-        static const long long min_groups = getenv("T2H_BX3_PERSIST_MIN_GROUPS") ? atoll(getenv("T2H_BX3_PERSIST_MIN_GROUPS")) : 4;
+        static const long long min_groups = env_ll("T2H_BX3_PERSIST_MIN_GROUPS", 4);
         long long groups = persist_wgs / (row_tiles > 0 ? row_tiles : 1);
         if (groups < min_groups) groups = min_groups;
         if (groups < 1) groups = 1;
@@ -1097,7 +1097,7 @@ WgradPlan bx3_wgrad_plan(int B, int H, int W, int Cin, int Cout) {
     p.n_units = B * H * (W / TW);
     const long long groups = (long long)(Cin / CC) * (Cout / (32 * p.cot));
     // ~512 workgroups; planes up to 128 x 128 (few units per workgroup either way): 256 -- half the slabs to write and reduce
-    static const long long forced = getenv("T2H_BX3_WGRAD_WGS") ? atoll(getenv("T2H_BX3_WGRAD_WGS")) : 0;
+    static const long long forced = env_ll("T2H_BX3_WGRAD_WGS", 0);
     const long long target = forced > 0 ? forced : ((long long)H * W <= 128 * 128 ? 256 : 512);
     long long splits = target / groups;
     if (splits < 1) splits = 1;
@@ -1285,7 +1285,7 @@ T2H_API int t2h_gemm_bx3(const float *x, int ldx, const void *wf, const float *b
 
 // ---- the weight gradient of the same GEMM: dW [N][K] = dY^T X, reduction over the M rows (bx3_wgrad_kernel<.., GT = K / 32>) ----------
 static int gemm_wgrad_splits(int64_t M, int N) {
-    static const long long target = getenv("T2H_GEMM_BX3_WGRAD_WGS") ? atoll(getenv("T2H_GEMM_BX3_WGRAD_WGS")) : 4096;
+    static const long long target = env_ll("T2H_GEMM_BX3_WGRAD_WGS", 4096);
     const long long groups = N / 64, units = M / TW;
     long long splits = (target + groups - 1) / groups;
     if (splits > units) splits = units;
@@ -1392,7 +1392,7 @@ static WgradPlan up_wgrad_plan(int B, int H, int W, int Cin, int Cout) {
     p.cot = Cin % 128 == 0 ? 4 : 2;
     p.n_units = (int)((long long)B * H * W / TW);
     const long long groups = (long long)(Cout / CC) * (Cin / (32 * p.cot));
-    static const long long forced = getenv("T2H_BX3_UPWGRAD_WGS") ? atoll(getenv("T2H_BX3_UPWGRAD_WGS")) : 0;
+    static const long long forced = env_ll("T2H_BX3_UPWGRAD_WGS", 0);
     long long splits = (forced > 0 ? forced : 256) / groups;
     if (splits < 1) splits = 1;
     if (splits > p.n_units) splits = p.n_units;

@@ -518,8 +518,8 @@ static int launch_gemm_kwaves(const GemmArgs &a, hipStream_t s, const char *what
 }
 // few output tiles (every CU would not even get one 64 x 64 tile's worth) and a reduction long enough to split
 static bool kwaves_applicable(long long rows, int cols, int depth) {
-    static const int min_k = [] { const char *e = getenv("T2H_KWAVES_MIN_K"); return e ? atoi(e) : 256; }();
-    static const long long max_tiles = [] { const char *e = getenv("T2H_KWAVES_MAX_TILES"); return e ? atoll(e) : 1024ll; }();
+    static const int min_k = (int)env_ll("T2H_KWAVES_MIN_K", 256);
+    static const long long max_tiles = env_ll("T2H_KWAVES_MAX_TILES", 1024);
     return depth >= min_k && ((rows + 31) / 32) * ((cols + 31) / 32) <= max_tiles;
 }
 
@@ -545,12 +545,17 @@ static int launch_rows_p(const GemmArgs &a, hipStream_t s, const char *what) {
     // 33 .. 64 output columns from a long reduction (the level products of the deferred point update at r = 256: 65536 pixel
     // rows x 2560 stacked columns -> 64): the A operand is streamed once, so smaller row tiles = more workgroups in flight
     // (64 x 64 x 32: 222 -> 207 us; 64-deep slabs or 32-row tiles: 262 / 332 us)
-    static const bool skinny = !(getenv("T2H_SKINNY") && getenv("T2H_SKINNY")[0] == '0');
+    static const bool skinny = env_flag("T2H_SKINNY", true);
     if (MODE == 0 && a.N > 32 && a.K >= 512 && skinny) return launch_gemm<64, 64, 2, 2, true, B_KC, 32, true, 1, 0>(a, 1, s, what);
     if (a.N > 32) return launch_gemm<128, 64, 2, 2, true, B_KC, 16, true, 1, MODE>(a, 1, s, what);
     return launch_gemm<128, 32, 4, 1, true, B_KC, 16, true, 1, MODE>(a, 1, s, what);
 }
 static int mode_of(int flags) { return (flags & T2H_BF16X3) ? 2 : ((flags & T2H_BF16) ? 1 : 0); }
+// the LDS-DMA kernels of gemm_dma.hip, forward / data gradient and the TN weight gradient alike (0: the register-staged kernels, A/B)
+static bool gemm_dma_enabled() {
+    static const bool on = env_flag("T2H_GEMM_DMA", true);
+    return on;
+}
 template <bool B_KC>
 static int launch_rows(const GemmArgs &a, int mode, hipStream_t s, const char *what) {
     // bf16: conversion-at-staging kernel (gemm_split.hip).  bf16x3 forward / data gradient: the in-loop split below is
@@ -566,7 +571,7 @@ static int launch_rows(const GemmArgs &a, int mode, hipStream_t s, const char *w
         const long long t128 = (long long)((a.M + 127) / 128) * ((a.N + 127) / 128);
         if (t128 < 192) {
             const long long t64 = (long long)((a.M + 63) / 64) * ((a.N + 63) / 64);
-            static const int small_bk = [] { const char *e = getenv("T2H_SMALLM_BK"); return e ? atoi(e) : 64; }();
+            static const int small_bk = (int)env_ll("T2H_SMALLM_BK", 64);
             if (kwaves_applicable(a.M, a.N, a.K)) return launch_gemm_kwaves<true, B_KC>(a, s, what);
             if (t64 >= 192) {
                 if (small_bk >= 32) return launch_gemm<64, 64, 2, 2, true, B_KC, 32, true, 1, 0>(a, 1, s, what);
@@ -577,10 +582,9 @@ static int launch_rows(const GemmArgs &a, int mode, hipStream_t s, const char *w
             return launch_gemm<32, 32, 1, 1, true, B_KC, 16, true, 1, 0>(a, 1, s, what);
         }
     }
-    static const bool use_dma = !(getenv("T2H_GEMM_DMA") && getenv("T2H_GEMM_DMA")[0] == '0');
     // (r02 A/B: 128 x 64 tiles for the 128- / 256-wide layers -- twice the workgroups, VERDICT r01 item 6 -- lose 5-14 % on
     // the forward and gain 10 % only on the data gradient into 256 columns from a 128-long reduction; not adopted)
-    if (use_dma && gemm_dma_applicable(B_KC, a)) return launch_gemm_dma(B_KC, a, s, what);
+    if (gemm_dma_enabled() && gemm_dma_applicable(B_KC, a)) return launch_gemm_dma(B_KC, a, s, what);
     return launch_rows_p<B_KC, 0>(a, s, what);
 }
 
@@ -788,7 +792,7 @@ T2H_API int t2h_linear_wgrad(const float *dy, int lddy, const float *x, int ldx,
         // the grid-side products of the deferred point update at r = 32 (1024 pixel rows, no bias gradient; 4096 rows and more: the
         // split launch + slab reduction below is faster, 70 vs 87 us at [2176, 256]): one launch, the
         // workgroup's four waves split the rows (gemm_kwaves_kernel), dW stored (or accumulated) directly
-        static const int kwaves_wgrad_max_rows = [] { const char *e = getenv("T2H_KWAVES_WGRAD_MAX_ROWS"); return e ? atoi(e) : 1024; }();
+        static const int kwaves_wgrad_max_rows = (int)env_ll("T2H_KWAVES_WGRAD_MAX_ROWS", 1024);
         if (!a.k_limit && mode == 0 && !db && M <= kwaves_wgrad_max_rows && aligned4(dw, K) && kwaves_applicable(N, K, M)) {
             a.C = dw; a.colsum = nullptr; a.k_chunk = M; a.slab_stride = 0;
             if (accumulate) a.flags |= F_ACCUM;
@@ -798,9 +802,8 @@ T2H_API int t2h_linear_wgrad(const float *dy, int lddy, const float *x, int ldx,
     (mode == 2 ? launch_gemm<BM_, BN_, WM_, WN_, false, false, 16, true, (MW_ > 2 ? 2 : MW_), 2>(a, p.splits, s, "linear_wgrad") \
      : mode == 1 ? launch_gemm<BM_, BN_, WM_, WN_, false, false, 16, true, (MW_ > 3 ? 3 : MW_), 1>(a, p.splits, s, "linear_wgrad") \
                  : launch_gemm<BM_, BN_, WM_, WN_, false, false, 16, true, MW_, 0>(a, p.splits, s, "linear_wgrad"))
-        static const bool tn_dma = !(getenv("T2H_GEMM_DMA") && getenv("T2H_GEMM_DMA")[0] == '0');
         if (a.k_limit && mode != 0) return fail(T2H_ERR_ARG, "linear_wgrad: a row limit needs the fp32 kernels");
-        if (p.bm == 128 && p.bn == 128 && mode == 0 && tn_dma && !a.k_limit && gemm_dma_tn_applicable(a))
+        if (p.bm == 128 && p.bn == 128 && mode == 0 && gemm_dma_enabled() && !a.k_limit && gemm_dma_tn_applicable(a))
             rc = launch_gemm_dma_tn(a, p.splits, s, "linear_wgrad");
         else if (p.bm == 128 && p.bn == 128)
             rc = mode != 0 ? launch_gemm_split(mode, false, false, a, p.splits, s, "linear_wgrad") : T2H_WG(128, 128, 2, 2, 4);

@@ -1798,7 +1798,7 @@ static int check_level(const char *what, int B, int nbits, int level, int C) {
 
 // the matrix-core form of the sample adjoint's per-cell partials: 64-channel wave slices (T2H_CELLS_MFMA=0: the VALU form, A/B)
 static bool cells_mfma(int C) {
-    static const bool on = !(getenv("T2H_CELLS_MFMA") && getenv("T2H_CELLS_MFMA")[0] == '0');
+    static const bool on = env_flag("T2H_CELLS_MFMA", true);
     return on && C % 64 == 0;
 }
 
@@ -1816,7 +1816,7 @@ static CoarsePlan coarse_plan(int B, int N, int nbits, int level, int C, int min
     // aim at >= 4096 workgroups; the channel chunks of a cell are workgroups of their own, so wide rows need fewer row
     // splits -- and every split costs a 9-slot partial row per cell to write and re-read (C = 512, r = 32: 4 -> 2 splits)
     const int64_t wgs = (int64_t)B * cells * p.chunks;
-    static const int64_t min_wgs = getenv("T2H_CELLS_MIN_WGS") ? atoll(getenv("T2H_CELLS_MIN_WGS")) : 4096;
+    static const int64_t min_wgs = env_ll("T2H_CELLS_MIN_WGS", 4096);
     int64_t want = (min_wgs + wgs - 1) / wgs;
     p.S = (int)(want < 1 ? 1 : (want > 8 ? 8 : want));
     return p;
@@ -2199,7 +2199,7 @@ T2H_API int t2h_sample_bwd_from_sums_ordered(const float *const *gplanes_nhwc, c
     int G = 1 << cp.lgG, P = kCellThreads >> cp.lgG;
     // table level of the matrix-core kernel: two levels finer than the sampling level (16 entries), not finer than the
     // finest plane; -1 (no table) when no plane would go into it or the rows per workgroup would not repay building it
-    static const int table_on = getenv("T2H_CELLS_TABLE") ? atoi(getenv("T2H_CELLS_TABLE")) : 1;
+    static const int table_on = (int)env_ll("T2H_CELLS_TABLE", 1);
     int tlevel = -1;
     if (table_on && C % 256 == 0) {
         int finest = nbits;

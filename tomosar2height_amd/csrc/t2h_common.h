@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdarg.h>
+#include <stdlib.h>
 
 #include "../../include/t2h.h"
 
@@ -23,6 +24,11 @@ void note_kernel(const char *name);
 const char *noted_kernel();
 
 inline hipStream_t as_stream(t2h_stream_t s) { return reinterpret_cast<hipStream_t>(s); }
+
+// ---- T2H_* environment switches: the library's only readers of the environment; each name is a library=True row of
+// tomosar2height_amd/switches.py, read at ONE site.  A flag is off only when the value starts with '0'; a number is atoll of it.
+inline bool env_flag(const char *name, bool dflt) { const char *e = getenv(name); return e ? e[0] != '0' : dflt; }
+inline long long env_ll(const char *name, long long dflt) { const char *e = getenv(name); return e ? atoll(e) : dflt; }
 
 // (B, N) of the point-side entry points: B tiles of N rows each -- or, N < 0, a RAGGED batch of B tiles with -N rows in all
 // (t2h_tile_build_ragged: tile boundaries are in off0 / the cell codes, and a row's tile index is kept as int bits in the LAST

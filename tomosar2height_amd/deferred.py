@@ -23,23 +23,23 @@ that run point-wise (narrow levels, where the per-point products are cheap): def
 least ``DEFER_MIN_CHANNELS`` channels on which the grid-first exchange applies (T2H_DEFER_MIN_CHANNELS, 0 = off).
 """
 import ctypes
-import os
 
 import torch
 
 from . import _lib, mlp, ops
+from . import switches
 
-DEFER_MIN_CHANNELS = int(os.environ.get("T2H_DEFER_MIN_CHANNELS", "128"))
-FUSED_SAMPLE_BWD = os.environ.get("T2H_FUSED_SAMPLE_BWD", "1") != "0"      # A/B: 0 = separate gather + sample adjoint
-CELLS_MFMA = os.environ.get("T2H_CELLS_MFMA", "1") != "0"                  # (mirrors the library's switch: the bit mask needs it)
-SIGN_BITS = os.environ.get("T2H_SIGN_BITS", "1") != "0"                    # A/B: 0 = keep the hidden activations for the mask
-ON_CHIP_HIDDEN = os.environ.get("T2H_ON_CHIP_HIDDEN", "1") != "0"          # A/B: 0 = sample kernel + per-cell sum kernel
+DEFER_MIN_CHANNELS = switches.get("T2H_DEFER_MIN_CHANNELS")
+FUSED_SAMPLE_BWD = switches.get("T2H_FUSED_SAMPLE_BWD")
+CELLS_MFMA = switches.get("T2H_CELLS_MFMA")                  # (mirrors the library's switch: the bit mask needs it)
+SIGN_BITS = switches.get("T2H_SIGN_BITS")
+ON_CHIP_HIDDEN = switches.get("T2H_ON_CHIP_HIDDEN")
 # A/B: 0 = one row per CELL in the sum matrices of every resolution.  1: the matrices of the finest deferred resolution hold one row
 # per OCCUPIED cell (cell_rows; decided statically per level -- the occupied fraction is known on the device only, and a host read
 # of it would be a sync in the step; where every cell is occupied, compact and dense rows coincide)
-COMPACT_SUMS = os.environ.get("T2H_COMPACT_SUMS", "1") != "0"
+COMPACT_SUMS = switches.get("T2H_COMPACT_SUMS")
 _empty = torch.empty          # allocator of the sum / gradient / product matrices (tests fill the new memory with NaN through it)
-ON_CHIP_MIN_PTS_PER_CELL = float(os.environ.get("T2H_ON_CHIP_MIN_PTS", "8"))   # the walk is sequential inside a cell
+ON_CHIP_MIN_PTS_PER_CELL = switches.get("T2H_ON_CHIP_MIN_PTS")
 
 
 # ------------------------------------------------------------------------------------------------ per-cell sums

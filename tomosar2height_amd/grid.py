@@ -13,16 +13,16 @@ runs in channels_last mode and otherwise keep the plain torch composition.
 """
 import ctypes
 import contextlib
-import os
 import weakref
 
 import torch
 import torch.nn.functional as F
 
 from . import _lib, mlp
+from . import switches
 
 # A/B switch: T2H_HIP_CONV=0 keeps every convolution on MIOpen (an explicit request, so it also allows the fallbacks)
-USE_HIP_CONV = os.environ.get("T2H_HIP_CONV", "1") != "0"
+USE_HIP_CONV = switches.get("T2H_HIP_CONV")
 if not USE_HIP_CONV:
     _lib.allow_library_fallback(True).set()
 
@@ -128,11 +128,11 @@ def conv3x3_supported(x: torch.Tensor, conv: torch.nn.Conv2d) -> bool:
 #   'fp32'             conv.hip's fp32 MFMA kernels (A/B; same tolerance: tests/test_hip_conv.py measures all three against float64)
 #   'bf16'             (set by TomoSAR2Height.set_mlp_precision('bf16'), BASELINE configs[2]) the leading bf16 part of both operands
 #                      only: one MFMA per product, tolerance of that MODE 2e-2 of the height scale (tests/test_full_size_vs_oracle.py)
-CONV_PRECISION = os.environ.get("T2H_CONV_PRECISION", "f16x2")
-BX3_MIN_PIXELS = int(os.environ.get("T2H_BX3_MIN_PIXELS", str(32 * 32)))
-_CONV_PRECISIONS = ("fp32", "bf16x3", "f16x2", "bf16")
-if CONV_PRECISION not in _CONV_PRECISIONS:
-    raise ValueError(f"T2H_CONV_PRECISION={CONV_PRECISION!r}: expected one of {_CONV_PRECISIONS}")
+CONV_PRECISION = switches.get("T2H_CONV_PRECISION")
+BX3_MIN_PIXELS = switches.get("T2H_BX3_MIN_PIXELS")
+# (the table refuses any other value of the variable at import, as the check that stood here did; set_conv_precision refuses
+# it for a caller)
+_CONV_PRECISIONS = switches.SWITCHES["T2H_CONV_PRECISION"]["kind"]
 _DEFAULT_CONV_PRECISION = CONV_PRECISION
 
 
@@ -265,7 +265,7 @@ class SplitWeightCache:
 
 
 split_weights = SplitWeightCache()
-BX3_WGRAD = os.environ.get("T2H_BX3_WGRAD", "1") != "0"        # A/B: 0 = weight gradients stay on conv.hip
+BX3_WGRAD = switches.get("T2H_BX3_WGRAD")
 
 
 def conv3x3_fwd_(x, w, bias, y, relu=False, accumulate=False):
@@ -288,7 +288,7 @@ def conv3x3_fwd_(x, w, bias, y, relu=False, accumulate=False):
 
 # r06: the 1 x 1 head's rank-1 share of a decoder activation's gradient formed in the data gradient's epilogue (T2H_HEAD_RANK1=0: the
 # head writes it, the data gradient accumulates onto it -- bit-identical)
-HEAD_RANK1 = os.environ.get("T2H_HEAD_RANK1", "1") != "0"
+HEAD_RANK1 = switches.get("T2H_HEAD_RANK1")
 
 
 def dgrad_rank1_ok(gy, w) -> bool:
@@ -397,7 +397,7 @@ class _Conv3x3(torch.autograd.Function):
 
 
 # planes whose weight gradients go to the trainer's side stream (r04d: all of them -- 8.29 -> 8.14 ms per step against 128 x 128)
-OVERLAP_MAX_PIXELS = int(os.environ.get("T2H_OVERLAP_CONV_MAX_PIXELS", str(512 * 512)))
+OVERLAP_MAX_PIXELS = switches.get("T2H_OVERLAP_CONV_MAX_PIXELS")
 
 
 def _conv3x3_param_grads(gm, x, weight, bias):
@@ -571,7 +571,7 @@ def upconv2x2_supported(x: torch.Tensor, conv) -> bool:
             and x.dtype == torch.float32 and _pow2(x.shape[2]) and _pow2(x.shape[3]))
 
 
-UPCONV_BX3 = os.environ.get("T2H_UPCONV_BX3", "1") != "0"      # A/B: 0 = transposed convolutions stay on conv.hip (fp32 MFMA)
+UPCONV_BX3 = switches.get("T2H_UPCONV_BX3")
 
 
 def _up_bx3(x, weight, w) -> bool:

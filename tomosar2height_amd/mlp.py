@@ -10,12 +10,12 @@ half in place.  There is no CPU path here: all tensors must live on the device.
 """
 import contextlib
 import ctypes
-import os
 from typing import Optional
 
 import torch
 
 from . import _lib, ops
+from . import switches
 from .ops import _rows, pool_max_fwd_ as _pool_fwd_        # (_pool_fwd_: the name tests launch the pooling by)
 
 
@@ -53,18 +53,18 @@ def _pflag() -> int:
 # ------------------------------------------------------------------------------------------------ kernel calls
 # Grid-side products of the deferred point update (deferred.py) on the bf16 matrix cores with the exact 3-way split
 # (csrc/conv_bx3.hip, 1-tap form; fp32-grade like the convolutions): T2H_GEMM_BX3=0 keeps them on the fp32 MFMA kernels (A/B)
-GEMM_BX3 = os.environ.get("T2H_GEMM_BX3", "1") != "0"
+GEMM_BX3 = switches.get("T2H_GEMM_BX3")
 
 
-_BX3_MIN_N = int(os.environ.get("T2H_GEMM_BX3_MIN_N", "64"))
-_BX3_MIN_K = int(os.environ.get("T2H_GEMM_BX3_MIN_K", "128"))
+_BX3_MIN_N = switches.get("T2H_GEMM_BX3_MIN_N")
+_BX3_MIN_K = switches.get("T2H_GEMM_BX3_MIN_K")
 # (r06: the transposed product dW = dY^T X of those matrices on the split kernels too, t2h_gemm_bx3_wgrad.  OFF by default: 215 against
 # 232 us per tile on the r = 256 level's [N = 2752, K = 64] at four tiles per launch, 248 against 280 at one -- its 32-row units of
 # 256-byte row segments keep it at 3.4 TB/s, not at the HBM floor the arithmetic would allow; profiles/r06_level256_probe.txt)
-_GEMM_BX3_WGRAD = os.environ.get("T2H_GEMM_BX3_WGRAD", "0") == "1"
-_BX3_WGRAD_MIN_N = int(os.environ.get("T2H_GEMM_BX3_WGRAD_MIN_N", "1024"))
-_BX3_WGRAD_MIN_M = int(os.environ.get("T2H_GEMM_BX3_WGRAD_MIN_M", "4096"))
-_PERSIST_N = os.environ.get("T2H_BX3_PERSIST_N", "1") != "0"
+_GEMM_BX3_WGRAD = switches.get("T2H_GEMM_BX3_WGRAD")
+_BX3_WGRAD_MIN_N = switches.get("T2H_GEMM_BX3_WGRAD_MIN_N")
+_BX3_WGRAD_MIN_M = switches.get("T2H_GEMM_BX3_WGRAD_MIN_M")
+_PERSIST_N = switches.get("T2H_BX3_PERSIST_N")      # (mirrors the library's switch: the routing below needs it)
 
 
 def _bx3_gemm_ok(m, k, n, *rows, force=False) -> bool:
@@ -507,7 +507,7 @@ def comm_mlp(sampled, w_a, b_a, w_b, b_b, c_last, w_c, b_c) -> torch.Tensor:
 # products.  Same function, different association of the fp32 sums (1e-6 relative); per level it removes one of the three
 # per-point GEMM triples (forward, data gradient, weight gradient).  GRID_FIRST_MIN_RATIO = points per pixel from which the
 # path is taken (0 switches it off: A/B).
-GRID_FIRST_MIN_RATIO = float(os.environ.get("T2H_GRID_FIRST_MIN_RATIO", "4"))
+GRID_FIRST_MIN_RATIO = switches.get("T2H_GRID_FIRST_MIN_RATIO")
 
 
 def grid_first_applicable(tile, r: int, c: int) -> bool:
@@ -567,7 +567,7 @@ def comm_mlp_grid_first(tile, plane, w_a, b_a, w_b, b_b, c_last, w_c, b_c):
 
 
 # ------------------------------------------------------------------------------------------------ PointNet trunk
-FUSED_TRUNK = os.environ.get("T2H_FUSED_TRUNK", "1") != "0"      # A/B switch: 0 = one GEMM launch per Linear + pool kernels
+FUSED_TRUNK = switches.get("T2H_FUSED_TRUNK")
 
 
 def _split_params(params):
@@ -607,10 +607,10 @@ def _fused_trunk_applicable(pts, w_pos, blocks, w_c) -> bool:
 # its pooling (fused_pool_cells) it is ahead at every size measured: 453 against 726 us at four tiles per launch, 143 against 193 at
 # one, 40 against 58 at 7 k rows, the 9 us that build a tile's work units included once (profiles/r06_trunk_fused.txt).
 # T2H_TRUNK_FUSED: "auto" (default) and "1": one launch from _TRUNK_FUSED_MIN_ROWS rows on, "0" never (one launch per block)
-_TRUNK_FUSED = os.environ.get("T2H_TRUNK_FUSED", "auto") != "0"
+_TRUNK_FUSED = switches.get("T2H_TRUNK_FUSED") != "0"
 _TRUNK_FUSED_MIN_ROWS = 0                    # the one launch is faster at every size (profiles/r06_trunk_fused.txt)
-_TRUNK_FUSED_STRIDE = int(os.environ.get("T2H_TRUNK_FUSED_STRIDE", "0"))
-_TRUNK_UNIT_BOUNDS = os.environ.get("T2H_TRUNK_UNIT_BOUNDS", "1") != "0"     # greedy units built once per tile index (0: fixed-stride windows looked up in the kernel)
+_TRUNK_FUSED_STRIDE = switches.get("T2H_TRUNK_FUSED_STRIDE")
+_TRUNK_UNIT_BOUNDS = switches.get("T2H_TRUNK_UNIT_BOUNDS")
 
 
 def _trunk_forward_one_launch(tile, pts, w_pos, b_pos, blocks, w_c, b_c):

@@ -6,11 +6,11 @@ Reference seam: ``pool_local`` (pointnet.py:92-99), ``generate_pl
 (pixel.py:107).  No op here has a torch/CPU fallback.
 """
 import atexit
-import os
 
 import torch
 
 from . import _lib
+from . import switches
 from .tile import TileIndex
 
 
@@ -262,8 +262,8 @@ def rasterise_mean(tile: TileIndex, feat: torch.Tensor, reso: int, channels_last
 # (N = 131072: r = 256 -- product 16-21 us against 60-80 us for the gather, build 47 us once for the level's three calls;
 # at r = 128 the product is 57 us against 73 us and no longer pays for its build); above SAMPLE_ADJOINT_MAX_ROWS rows per
 # pixel t2h_sample_bwd's gather / per-cell partials stay.  T2H_SAMPLE_ADJOINT=0 switches the path off (A/B).
-SAMPLE_ADJOINT = os.environ.get("T2H_SAMPLE_ADJOINT", "1") != "0"
-SAMPLE_ADJOINT_MAX_ROWS = float(os.environ.get("T2H_SAMPLE_ADJOINT_MAX_ROWS", "4"))
+SAMPLE_ADJOINT = switches.get("T2H_SAMPLE_ADJOINT")
+SAMPLE_ADJOINT_MAX_ROWS = switches.get("T2H_SAMPLE_ADJOINT_MAX_ROWS")
 
 
 def _sample_bwd(tile, gout, r, c, addend):
@@ -484,8 +484,7 @@ def coordinate2index(x: torch.Tensor, reso: int) -> torch.Tensor:
 # modules never take this route (they keep features in sorted order).
 _index_tiles = {}          # id(index tensor) -> (weakref, (version, data_ptr, shape, device), cells, TileIndex, ready event, stream)
 _pending_index_checks = []  # (event, pinned status copy, description)
-# T2H_SEAM_SYNC_CHECK=1 (debugging): every seam call waits for its own index check and raises at the call, like torch_scatter
-_SYNC_CHECK = os.environ.get("T2H_SEAM_SYNC_CHECK", "0") == "1"
+_SYNC_CHECK = switches.get("T2H_SEAM_SYNC_CHECK")
 
 
 def forget_index(index: torch.Tensor = None):

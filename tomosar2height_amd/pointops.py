@@ -17,11 +17,10 @@ The entry points of include/t2h_pnpp.h are bound here: ``_lib.declare("t2h_pnpp.
 """
 import ctypes
 import numbers
-import os
 
 import torch
 
-from . import _lib
+from . import _lib, switches
 
 _vp, _i, _i64, _sz, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
 
@@ -56,11 +55,10 @@ load = _lib.load
 
 def fps_slice(n: int) -> int:
     """Points per workgroup ``farthest_point_sample`` will use on an N-point cloud (0: the one-workgroup form)."""
-    env = os.environ.get("T2H_FPS_SLICE")
-    if env:
-        s = int(env)
+    s = switches.get("T2H_FPS_SLICE")
+    if s is not None:
         if s < 64 or s % 64:
-            raise ValueError(f"T2H_FPS_SLICE={env}: a multiple of 64 is needed")
+            raise ValueError(f"T2H_FPS_SLICE={s}: a multiple of 64 is needed")
         return s
     return 0 if n <= FPS_ONE_WG_MAX else FPS_SLICE_DEFAULT
 

@@ -12,14 +12,13 @@ single-device accumulated gradient.  Parameters that never receive a gradient
 AdamW skips them exactly as it does in the reference.
 """
 import contextlib
-import os
 from collections import defaultdict
 
 import torch
 import torch.distributed as dist
 import torch.nn as nn
 
-from . import _lib, mlp
+from . import _lib, mlp, switches
 
 
 def _is_dense(t: torch.Tensor) -> bool:
@@ -93,22 +92,22 @@ class Trainer:
         self.local_every = optimize_every // self.world      # tiles per rank per optimizer step
         self.bucket = None
         self._graph = None
-        self.direct_accumulation = os.environ.get("T2H_DIRECT_ACCUM", "1") != "0"
+        self.direct_accumulation = switches.get("T2H_DIRECT_ACCUM")
         # weight-gradient GEMMs on a side stream (see mlp.direct_grad_accumulation), joined at the end of every train_step's
         # backward (T2H_OVERLAP_WGRAD=0: A/B).  On by default since r04: with the fp16-split convolutions most launches of a
         # B = 1 step leave CUs idle (8.94 -> 8.71 ms with both overlaps).  bench.py switches them off for its untimed per-kernel leg
         # (--profile-steps), so the durations of its kernel table stay those of kernels running alone
-        self.overlap_wgrad = os.environ.get("T2H_OVERLAP_WGRAD", "1") == "1"
+        self.overlap_wgrad = switches.get("T2H_OVERLAP_WGRAD")
         self._side = None
         # the weight gradients of the convolutions on planes up to 128 x 128 (latency-bound launches that leave most CUs idle)
         # beside the following layers' data gradients: T2H_OVERLAP_CONV_WGRAD=1
-        self.overlap_conv_wgrad = os.environ.get("T2H_OVERLAP_CONV_WGRAD", "1") == "1"
+        self.overlap_conv_wgrad = switches.get("T2H_OVERLAP_CONV_WGRAD")
         self._conv_side = None
         # the tiles of an accumulation window are independent: tile i + 1's forward runs beside tile i's backward, each tile on
         # its own stream of a ping-pong pair (see ``_train_step_pipelined``); T2H_PIPELINE_TILES=0: one tile after the other
-        self.pipeline_tiles = os.environ.get("T2H_PIPELINE_TILES", "1") == "1"
+        self.pipeline_tiles = switches.get("T2H_PIPELINE_TILES")
         # ... and so do the micro-batches of a window (T2H_PIPELINE_MICRO_BATCHES=0: a micro-batch runs on the caller's stream alone)
-        self.pipeline_micro_batches = os.environ.get("T2H_PIPELINE_MICRO_BATCHES", "1") == "1"
+        self.pipeline_micro_batches = switches.get("T2H_PIPELINE_MICRO_BATCHES")
         self._tile_streams = None
         self._pending = None            # (loss, l1, ce, stream, weights version, graph set) of the tile whose backward is held back
         self._pipe_graphs = None        # capture_pipeline_graphs: forward / backward hipGraphs of the two tile streams
@@ -121,7 +120,7 @@ class Trainer:
         # (tomosar2height.yaml:40), and a B = 1 step is ~340 launches most of which leave the chip idle (r05: 144 -> 174 tiles/s
         # with the same kernels).  Never across an optimizer boundary; ``flush_gradients()`` / ``optimizer_boundary()`` issue what
         # is held.  T2H_COALESCE_TILES=1: every tile issued by its own call (the strict B = 1 step).
-        self.coalesce_tiles = max(1, int(os.environ.get("T2H_COALESCE_TILES", "4")))
+        self.coalesce_tiles = max(1, switches.get("T2H_COALESCE_TILES"))
         self._coalesced = []            # tiles accepted by train_step, not yet issued
         self._coalesced_version = None  # the weights' version counter when the first of them was accepted
 
@@ -133,7 +132,7 @@ class Trainer:
         # ``model(...).backward()`` -- never routes gradients into it and sees complete ``.grad`` (plain autograd).
         self.compose_cache = None
         self._unet = getattr(getattr(model, "point_encoder", None), "unet", None)
-        if os.environ.get("T2H_COMPOSE_CACHE", "1") != "0" and self._unet is not None and hasattr(self._unet, "forward_sorted"):
+        if switches.get("T2H_COMPOSE_CACHE") and self._unet is not None and hasattr(self._unet, "forward_sorted"):
             from . import deferred
             self.compose_cache = deferred.ComposeCache()
 
@@ -453,7 +452,7 @@ class Trainer:
         # (not with the side streams: there each reduction runs at once beside other kernels, which measures faster than one
         # batched launch on an otherwise idle chip -- 8.71 against 8.95 ms per step)
         batch = (direct and loss.is_cuda and side is None and conv_side is None
-                 and os.environ.get("T2H_BATCH_REDUCE", "1") != "0")
+                 and switches.get("T2H_BATCH_REDUCE"))
         with mlp.direct_grad_accumulation(direct, side, conv_side), _lib.reduce_capture(batch):
             loss.backward()
             for st in (side, conv_side):
