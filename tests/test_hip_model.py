@@ -849,6 +849,41 @@ def test_pipelined_tiles_as_hipgraphs_give_identical_gradients():
         assert torch.equal(wa[k], wb[k]), k
 
 
+@pytest.mark.parametrize("form", ["capture_graph", "capture_pipeline_graphs"])
+def test_capture_leaves_the_accumulators_as_they_were(form):
+    """Both capture forms run two warm-up steps and the captured one on the live gradient bucket, loss accumulators and compose
+    cache, and promise to leave them as they found them: bit for bit, so no tolerance."""
+    from tomosar2height_amd import TomoSAR2Height
+    from tomosar2height_amd.config import berlin_config
+    from tomosar2height_amd.trainer import Trainer
+    cfg = berlin_config()
+    cfg.model.encoder_kwargs.plane_resolution = 64
+    cfg.model.encoder_kwargs.unet_kwargs.depth = 3
+    tiles = [{"inputs": synth_cloud(5000, seed=500 + i).to(_dev()),
+              "dsm": (torch.rand(1, 512, 512, generator=torch.Generator().manual_seed(i)) * 30).to(_dev())} for i in range(3)]
+    model = det_init_(TomoSAR2Height(cfg), seed=12).to(_dev())
+    tr = Trainer(model, torch.optim.SGD(model.parameters(), lr=0.0), device=_dev(), optimize_every=100, use_cloud=True)
+    tr.coalesce_tiles = 1
+    if form == "capture_pipeline_graphs":
+        tr.pipeline_tiles = True
+        tr.overlap_wgrad = tr.overlap_conv_wgrad = False            # (the graphs keep the weight gradients on the tile's stream)
+    tr.train_step(tiles[0])
+    tr.train_step(tiles[1])
+    tr.flush_gradients()
+
+    def cache_tensors():
+        return [t for level in tr.compose_cache.snapshot()[0] for t in level] if tr.compose_cache is not None else []
+
+    grads, loss, steps, cache = tr.bucket.flat.clone(), float(tr.accumulated_loss), tr.accumulated_steps, cache_tensors()
+    assert steps == 2 and loss > 0 and grads.abs().max().item() > 0     # (something is there to be polluted)
+    getattr(tr, form)(tiles[2])
+    torch.cuda.synchronize()
+    assert torch.equal(tr.bucket.flat, grads)
+    assert float(tr.accumulated_loss) == loss and tr.accumulated_steps == steps
+    after = cache_tensors()
+    assert len(after) == len(cache) and all(torch.equal(a, b) for a, b in zip(after, cache))
+
+
 def test_tile_index_built_ahead_on_a_side_stream_gives_the_same_step():
     """``Trainer.prepare`` builds the next tile's index (cell sort, sampling adjoint, cell counts) on a side stream while the
     current step runs; the step on the prebuilt index is the step on the raw cloud, bit for bit (same kernels, same order)."""

@@ -12,7 +12,7 @@ single-device accumulated gradient.  Parameters that never receive a gradient
 AdamW skips them exactly as it does in the reference.
 """
 import contextlib
-from collections import defaultdict
+from collections import defaultdict, namedtuple
 
 import torch
 import torch.distributed as dist
@@ -64,6 +64,24 @@ class GradBucket:
         self.flat.zero_()
 
 
+class _Captured(namedtuple("_Captured", "fwd bwd static l1 ce loss shapes")):
+    """One tile step as hipGraphs for tiles of ``shapes``, read from the buffers ``static``: ``fwd`` is forward + loss and, where
+    ``bwd`` is None, the backward too; else ``bwd`` is the backward's own graph on ``fwd``'s memory pool."""
+
+    def matches(self, data) -> bool:
+        return all(data.get(k) is not None and tuple(getattr(data[k], "shape", ())) == shp for k, shp in self.shapes.items())
+
+    def replay_forward(self, data):
+        for k, buf in self.static.items():
+            buf.copy_(data[k], non_blocking=True)
+        self.fwd.replay()
+
+
+# a pipelined tile between its forward and its backward: ``version`` is the weights' version counter at the forward, ``gset`` the
+# _Captured whose ``bwd`` replays the backward (None: eager)
+_HeldTile = namedtuple("_HeldTile", "loss l1 ce stream version gset data")
+
+
 class Trainer:
     def __init__(self, model: nn.Module, optimizer, device=None, optimize_every=1, use_cloud=False, use_image=False,
                  use_footprint=False, weight_ce=10., process_group=None, check_domain=True, scheduler=None):
@@ -109,8 +127,8 @@ class Trainer:
         # ... and so do the micro-batches of a window (T2H_PIPELINE_MICRO_BATCHES=0: a micro-batch runs on the caller's stream alone)
         self.pipeline_micro_batches = switches.get("T2H_PIPELINE_MICRO_BATCHES")
         self._tile_streams = None
-        self._pending = None            # (loss, l1, ce, stream, weights version, graph set) of the tile whose backward is held back
-        self._pipe_graphs = None        # capture_pipeline_graphs: forward / backward hipGraphs of the two tile streams
+        self._pending = None            # the _HeldTile whose backward is held back
+        self._pipe_graphs = None        # capture_pipeline_graphs: one _Captured (forward / backward hipGraphs) per tile stream
         self._bwd_done = None           # event: end of the last issued backward (the next one accumulates into the same buffers)
         self._tile_parity = 0
         self._held = []                 # (event at the end of a tile's backward, that tile's ``data``): see _hold_inputs
@@ -131,15 +149,17 @@ class Trainer:
         # (``_own_cache``): a forward / backward issued by anybody else -- a second Trainer on the same model, a plain
         # ``model(...).backward()`` -- never routes gradients into it and sees complete ``.grad`` (plain autograd).
         self.compose_cache = None
-        self._unet = getattr(getattr(model, "point_encoder", None), "unet", None)
+        enc = self._point_encoder = getattr(model, "point_encoder", None)
+        self._unet = getattr(enc, "unet", None)
         if switches.get("T2H_COMPOSE_CACHE") and self._unet is not None and hasattr(self._unet, "forward_sorted"):
             from . import deferred
             self.compose_cache = deferred.ComposeCache()
 
-        enc = getattr(model, "point_encoder", None)
         if check_domain and enc is not None and hasattr(enc, "snapshot_domain"):
             enc.snapshot_domain = True          # the boundary's out-of-domain read waits for the last tile's index only (pointnet.py)
         self._flag_stream = None
+        self._modules_flat = None       # every submodule, listed at the first window (_any_submodule_in_eval)
+        self._sentinel = None           # one trained parameter (_weights_version)
         self.accumulated_steps = 0
         self.accumulated_loss = 0.0
         self.accumulated_loss_dict = {"loss_ce": 0.0, "loss_l1": 0.0}
@@ -164,18 +184,30 @@ class Trainer:
         finally:
             self._unet.compose_cache = prev
 
+    # ------------------------------------------------------------------------------------------ streams
+    def _lazy_streams(self, name, device, pair=False):
+        """The stream (``pair``: tuple of two streams) kept in attribute ``name``, created at its first use."""
+        st = getattr(self, name)
+        if st is None:
+            st = (torch.cuda.Stream(device=device), torch.cuda.Stream(device=device)) if pair else torch.cuda.Stream(device=device)
+            setattr(self, name, st)
+        return st
+
     # ------------------------------------------------------------------------------------------ per-tile statistics
     def _per_tile_statistics(self) -> bool:
         """True for a model whose point encoder normalises with BATCH statistics (``PointNetPlusPlus(batch_statistics=True)``).
         The reference's statistics are per tile (batch = 1), so such a model's tiles are issued one by one -- no coalescing, no
         micro-batch: the statistics would mix tiles -- and on one stream: every forward updates the running statistics, and
         consecutive updates must stay in order (no two-stream tile pipeline, no captured graph)."""
-        return bool(getattr(getattr(self.model, "point_encoder", None), "batch_statistics", False))
+        return bool(getattr(self._point_encoder, "batch_statistics", False))    # (read per call: a caller may flip it between windows)
 
     # ------------------------------------------------------------------------------------------ loss
     def _losses(self, data, mask_threshold):
         device = self.device
         if isinstance(data, (list, tuple)):
+            # two bodies on purpose, not this one with nb = 1: here the footprint mask compares the target in its OWN dtype, there
+            # after .float() (a float64 target near the threshold would change class), and a ``1 *`` here would be one more launch
+            # per loss in the strict B = 1 step and in every captured graph (tests/test_launch_census.py counts them)
             return self._losses_micro_batch(data, mask_threshold)
         input_cloud = data.get("inputs").to(device) if self.use_cloud else None
         input_image = data.get("image").to(device) if self.use_image else None
@@ -221,32 +253,8 @@ class Trainer:
             raise RuntimeError("capture_graph: run one eager train_step first (the gradient bucket must exist)")
         self.flush_pipeline()
         self._snapshots_off()
-        dev = self.device
-        static = {k: example[k].to(dev).clone() for k in ("inputs", "image", "dsm") if example.get(k) is not None}
-        self.model.train()
-        saved = self.bucket.flat.clone()                   # warm-up / capture passes must not pollute the accumulators
-        saved_cache = self.compose_cache.snapshot() if self.compose_cache is not None else None
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with self._own_cache():
-            with torch.cuda.stream(side):                  # warm-up on a side stream, as torch.cuda.graphs prescribes
-                for _ in range(2):
-                    l1, ce = self._losses(static, 0.0001)
-                    with mlp.direct_grad_accumulation(self.direct_accumulation):
-                        (l1 + ce).backward()
-            del l1, ce                                     # drop the warm-up autograd graph (and its AccumulateGrad nodes)
-            torch.cuda.current_stream(dev).wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph, stream=side):     # capture on the stream the warm-up ran on
-                l1, ce = self._losses(static, 0.0001)
-                with mlp.direct_grad_accumulation(self.direct_accumulation), _lib.reduce_capture(self.direct_accumulation):
-                    (l1 + ce).backward()
-        self.bucket.flat.copy_(saved)
-        if saved_cache is not None:
-            self.compose_cache.restore(saved_cache)
-        self._graph = {"graph": graph, "static": static, "l1": l1.detach(), "ce": ce.detach(),
-                       "shapes": {k: tuple(v.shape) for k, v in static.items()}}
-        return graph
+        self._graph = self._capture([torch.cuda.Stream(device=self.device)], example, split=False)[0]    # (on a stream of its own)
+        return self._graph.fwd
 
     def capture_pipeline_graphs(self, example):
         """The tile pipeline (``_train_step_pipelined``) as hipGraphs: for each stream of the ping-pong pair ONE graph of the
@@ -264,58 +272,51 @@ class Trainer:
             raise RuntimeError("capture_pipeline_graphs: run one eager train_step first (the gradient bucket must exist)")
         self._snapshots_off()
         self.flush_pipeline()
+        self._pipe_graphs = self._capture(self._lazy_streams("_tile_streams", self.device, pair=True), example, split=True)
+        return self._pipe_graphs
+
+    def _capture(self, streams, example, split):
+        """One ``_Captured`` per stream of ``streams``, for tiles of ``example``'s shapes: two warm-up steps on the stream, then the
+        capture on it -- forward + loss + backward as one graph, or (``split``) the backward as a second graph on the first one's
+        memory pool.  Gradient bucket and compose cache are saved once before and put back once after all of it."""
         dev = self.device
         main = torch.cuda.current_stream(dev)
-        if self._tile_streams is None:
-            self._tile_streams = (torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev))
         self.model.train()
         saved = self.bucket.flat.clone()                   # warm-up / capture passes must not pollute the accumulators
         saved_cache = self.compose_cache.snapshot() if self.compose_cache is not None else None
-        sets = []
-        for st in self._tile_streams:
+        captured = []
+        for st in streams:
             static = {k: example[k].to(dev).clone() for k in ("inputs", "image", "dsm") if example.get(k) is not None}
             st.wait_stream(main)
             with self._own_cache():
                 with torch.cuda.stream(st):                # warm-up on the capture stream, as torch.cuda.graphs prescribes
                     for _ in range(2):
                         l1, ce = self._losses(static, 0.0001)
-                        with mlp.direct_grad_accumulation(self.direct_accumulation):
-                            (l1 + ce).backward()
-                del l1, ce
+                        self._backward_in(l1 + ce, self.direct_accumulation, False)
+                del l1, ce                                 # drop the warm-up autograd graph (and its AccumulateGrad nodes)
                 main.wait_stream(st)
-                gf, gb = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gf, stream=st):
+                fwd, bwd = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph() if split else None
+                with torch.cuda.graph(fwd, stream=st):
                     l1, ce = self._losses(static, 0.0001)
                     loss = l1 + ce
-                with torch.cuda.graph(gb, stream=st, pool=gf.pool()):
-                    with mlp.direct_grad_accumulation(self.direct_accumulation), _lib.reduce_capture(self.direct_accumulation):
-                        loss.backward()
-            main.wait_stream(st)
-            sets.append({"fwd": gf, "bwd": gb, "static": static, "l1": l1.detach(), "ce": ce.detach(), "loss": loss.detach()})
+                    if not split:
+                        self._backward_in(loss, self.direct_accumulation, self.direct_accumulation)
+                if split:
+                    with torch.cuda.graph(bwd, stream=st, pool=fwd.pool()):
+                        self._backward_in(loss, self.direct_accumulation, self.direct_accumulation)
+            main.wait_stream(st)                           # (as after the warm-up; the capture itself queued nothing on ``st``)
+            captured.append(_Captured(fwd, bwd, static, l1.detach(), ce.detach(), loss.detach(),
+                                      {k: tuple(v.shape) for k, v in static.items()}))
         self.bucket.flat.copy_(saved)
         if saved_cache is not None:
             self.compose_cache.restore(saved_cache)
-        self._pipe_graphs = {"sets": sets, "shapes": {k: tuple(v.shape) for k, v in sets[0]["static"].items()}}
-        return self._pipe_graphs
+        return captured
 
     def _snapshots_off(self):
         """hipGraph replays run no Python per tile: the out-of-domain totals are then read from the device at the boundary (the
         snapshot's event record inside a capture could not be waited for from the host)."""
-        enc = getattr(self.model, "point_encoder", None)
-        if enc is not None and hasattr(enc, "snapshot_domain"):
-            enc.snapshot_domain = False
-
-    def _pipe_graphs_match(self, data) -> bool:
-        g = getattr(self, "_pipe_graphs", None)
-        if g is None:
-            return False
-        return all(data.get(k) is not None and tuple(getattr(data[k], "shape", ())) == shp for k, shp in g["shapes"].items())
-
-    def _graph_matches(self, data) -> bool:
-        g = getattr(self, "_graph", None)
-        if g is None:
-            return False
-        return all(data.get(k) is not None and tuple(getattr(data[k], "shape", ())) == shp for k, shp in g["shapes"].items())
+        if self._point_encoder is not None and hasattr(self._point_encoder, "snapshot_domain"):
+            self._point_encoder.snapshot_domain = False
 
     # ------------------------------------------------------------------------------------------ input pipeline
     def prepare(self, data, stream=None):
@@ -323,7 +324,7 @@ class Trainer:
         ``stream`` -- a side stream, so these small latency-bound kernels run beside the current tile's step instead of alone
         at the head of the next one.  Returns ``data`` with the cloud replaced by the prebuilt ``TileIndex``; results are the
         same as for the raw cloud.  (HIP model with a point encoder only; anything else is returned unchanged.)"""
-        enc = getattr(self.model, "point_encoder", None)
+        enc = self._point_encoder
         cloud = data.get("inputs") if self.use_cloud else None
         if enc is None or not hasattr(enc, "prepare") or not torch.is_tensor(cloud):
             return data
@@ -364,7 +365,11 @@ class Trainer:
         cloud = data.get("inputs") if self.use_cloud else None
         if self.use_cloud and not (torch.is_tensor(cloud) and cloud.dim() == 3 and cloud.shape[0] == 1):
             return False
-        return torch.is_tensor(data.get("dsm")) and next(self.model.parameters()).is_cuda
+        return self._device_tile(data)
+
+    def _device_tile(self, data) -> bool:
+        """A raw tile (a dict with a tensor target) for a model on the GPU."""
+        return isinstance(data, dict) and torch.is_tensor(data.get("dsm")) and next(self.model.parameters()).is_cuda
 
     def _flush_coalesced(self) -> bool:
         """Issue the tiles ``train_step`` holds back as one micro-batch.  True if that ended with an optimizer step."""
@@ -397,15 +402,13 @@ class Trainer:
                              f"(the reference's are per tile): hand the tiles to train_step one by one")
         first = data[0] if n_tiles > 1 else data
         if (not per_tile and self.pipeline_tiles and (n_tiles == 1 or self.pipeline_micro_batches) and self.bucket is not None and self._graph is None
-                and isinstance(first, dict) and torch.is_tensor(first.get("dsm")) and next(self.model.parameters()).is_cuda):
+                and self._device_tile(first)):
             return self._train_step_pipelined(data, n_tiles)
         self.flush_pipeline()
-        if n_tiles == 1 and self._graph_matches(data):
-            g = self._graph
-            for k, buf in g["static"].items():
-                buf.copy_(data[k], non_blocking=True)
-            g["graph"].replay()
-            loss_l1, loss_ce = g["l1"], g["ce"]
+        g = self._graph
+        if n_tiles == 1 and g is not None and g.matches(data):
+            g.replay_forward(data)
+            loss_l1, loss_ce = g.l1, g.ce
             loss = loss_l1 + loss_ce
         else:
             with self._own_cache():
@@ -418,34 +421,33 @@ class Trainer:
             # their .grad are views into one flat buffer that the wgrad kernels accumulate into directly
             self.bucket = GradBucket(list(self.model.parameters()))
 
+        self._account(loss, loss_l1, loss_ce)
+        return self._tiles_issued(n_tiles)
+
+    def _tiles_issued(self, n_tiles) -> bool:
+        """Count the tiles; at the end of the accumulation window run its optimizer step (True then)."""
         self.accumulated_steps += n_tiles
-        self.accumulated_loss += loss.detach()
-        self.accumulated_loss_dict["loss_ce"] += loss_ce.detach()
-        self.accumulated_loss_dict["loss_l1"] += loss_l1.detach()
         if self.accumulated_steps < self.local_every:
             return False
-
         self.optimizer_boundary()
         return True
 
+    def _account(self, loss, loss_l1, loss_ce):
+        """Add a tile's (micro-batch's) losses to the window's, on the current stream."""
+        self.accumulated_loss += loss.detach()
+        self.accumulated_loss_dict["loss_ce"] += loss_ce.detach()
+        self.accumulated_loss_dict["loss_l1"] += loss_l1.detach()
+
     def _any_submodule_in_eval(self) -> bool:
-        mods = getattr(self, "_modules_flat", None)
-        if mods is None:
-            mods = self._modules_flat = list(self.model.modules())
-        return any(not m.training for m in mods)
+        if self._modules_flat is None:
+            self._modules_flat = list(self.model.modules())
+        return any(not m.training for m in self._modules_flat)
 
     def _backward(self, loss):
         """``loss.backward()`` of one tile (or micro-batch) with the weight gradients on the side streams."""
-        side = None
-        if self.overlap_wgrad and self.bucket is not None and loss.is_cuda:
-            if self._side is None:
-                self._side = torch.cuda.Stream(device=loss.device)
-            side = self._side
-        conv_side = None
-        if self.overlap_conv_wgrad and self.bucket is not None and loss.is_cuda:
-            if self._conv_side is None:
-                self._conv_side = torch.cuda.Stream(device=loss.device)
-            conv_side = self._conv_side
+        overlap = self.bucket is not None and loss.is_cuda
+        side = self._lazy_streams("_side", loss.device) if self.overlap_wgrad and overlap else None
+        conv_side = self._lazy_streams("_conv_side", loss.device) if self.overlap_conv_wgrad and overlap else None
         direct = self.bucket is not None and self.direct_accumulation
         # the weight gradients accumulate straight into the bucket and nothing reads it before the pass ends: their slab
         # reductions run as ONE batched launch at the end of the pass instead of one launch per layer (T2H_BATCH_REDUCE=0: A/B)
@@ -453,6 +455,11 @@ class Trainer:
         # batched launch on an otherwise idle chip -- 8.71 against 8.95 ms per step)
         batch = (direct and loss.is_cuda and side is None and conv_side is None
                  and switches.get("T2H_BATCH_REDUCE"))
+        self._backward_in(loss, direct, batch, side, conv_side)
+
+    def _backward_in(self, loss, direct, batch, side=None, conv_side=None):
+        """``loss.backward()`` inside the two blocks every backward of the trainer runs in: weight gradients accumulated straight
+        into the bucket (``direct``; on the side streams, if any) and their slab reductions as one launch at the end (``batch``)."""
         with mlp.direct_grad_accumulation(direct, side, conv_side), _lib.reduce_capture(batch):
             loss.backward()
             for st in (side, conv_side):
@@ -474,37 +481,30 @@ class Trainer:
         CUs of a B = 1 step filled by the neighbouring tile."""
         dev = next(self.model.parameters()).device
         main = torch.cuda.current_stream(dev)
-        if self._tile_streams is None:
-            self._tile_streams = (torch.cuda.Stream(device=dev), torch.cuda.Stream(device=dev))
         parity = self._tile_parity
-        st = self._tile_streams[parity]
+        st = self._lazy_streams("_tile_streams", dev, pair=True)[parity]
         self._tile_parity ^= 1
         st.wait_stream(main)                                  # the tile's tensors, the weights of the last optimizer step
-        gset = self._pipe_graphs["sets"][parity] if (n_tiles == 1 and self._pipe_graphs_match(data)) else None
+        sets = self._pipe_graphs
+        gset = sets[parity] if (n_tiles == 1 and sets is not None and sets[parity].matches(data)) else None
         with torch.cuda.stream(st):
             if gset is not None:                              # (this stream's previous tile has finished with the static buffers:
-                for k, buf in gset["static"].items():         #  its backward graph precedes these copies in stream order)
-                    buf.copy_(data[k], non_blocking=True)
-                gset["fwd"].replay()
-                loss, loss_l1, loss_ce = gset["loss"], gset["l1"], gset["ce"]
+                gset.replay_forward(data)                     #  its backward graph precedes the copies into them in stream order)
+                loss, loss_l1, loss_ce = gset.loss, gset.l1, gset.ce
             else:
                 with self._own_cache():
                     loss_l1, loss_ce = self._losses(data, 0.0001)
                 loss = loss_l1 + loss_ce
         self._issue_pending_backward()
-        self._pending = (loss, loss_l1, loss_ce, st, self._weights_version(), gset, data)
-        self.accumulated_steps += n_tiles
-        if self.accumulated_steps < self.local_every:
-            return False
-        self.optimizer_boundary()
-        return True
+        self._pending = _HeldTile(loss, loss_l1, loss_ce, st, self._weights_version(), gset, data)
+        return self._tiles_issued(n_tiles)
 
     def _issue_pending_backward(self):
         if self._pending is None:
             return
-        loss, loss_l1, loss_ce, st, version, gset, data = self._pending
-        self._pending = None
-        if version != self._weights_version():
+        tile, self._pending = self._pending, None
+        st = tile.stream
+        if tile.version != self._weights_version():
             self._reset_accumulators()
             raise RuntimeError("the weights changed (an optimizer step outside the Trainer?) while the backward of the previous tile "
                                "was still unflushed in the tile pipeline: call Trainer.flush_gradients() before stepping an "
@@ -512,17 +512,15 @@ class Trainer:
         if self._bwd_done is not None:
             st.wait_event(self._bwd_done)                     # the previous tile's backward has the same accumulators
         with torch.cuda.stream(st):
-            if gset is not None:
-                gset["bwd"].replay()
+            if tile.gset is not None:
+                tile.gset.bwd.replay()
                 if self.compose_cache is not None:
                     self.compose_cache.pending = True         # (what the eager backward notes in Python)
             else:
-                self._backward(loss)
-            self.accumulated_loss += loss.detach()
-            self.accumulated_loss_dict["loss_ce"] += loss_ce.detach()
-            self.accumulated_loss_dict["loss_l1"] += loss_l1.detach()
+                self._backward(tile.loss)
+            self._account(tile.loss, tile.l1, tile.ce)
             self._bwd_done = st.record_event(torch.cuda.Event(enable_timing=True))
-        self._hold_inputs(self._bwd_done, data)
+        self._hold_inputs(self._bwd_done, tile.data)
 
     def _hold_inputs(self, done, data):
         """The caller's tensors of a pipelined tile -- cloud or prebuilt TileIndex, target, image -- were allocated on the
@@ -539,10 +537,9 @@ class Trainer:
 
     def _weights_version(self) -> int:
         """Version counter of one trained parameter (every optimizer, FlatAdamW included, bumps all of them together)."""
-        p = getattr(self, "_sentinel", None)
-        if p is None:
-            p = self._sentinel = next(q for q in self.model.parameters() if q.requires_grad)
-        return p._version
+        if self._sentinel is None:
+            self._sentinel = next(q for q in self.model.parameters() if q.requires_grad)
+        return self._sentinel._version
 
     def step_event(self):
         """A timing-enabled event at the end of the GPU work of the most recent tile whose backward has been issued (the tile
@@ -561,9 +558,12 @@ class Trainer:
         if self._pending is None and self._bwd_done is None:
             return
         self._issue_pending_backward()
-        main = torch.cuda.current_stream()
+        self._join_tile_streams()
+
+    def _join_tile_streams(self):
+        """The calling stream waits for what the tile streams (if there are any) have queued."""
         for st in self._tile_streams or ():
-            main.wait_stream(st)
+            torch.cuda.current_stream().wait_stream(st)
         self._bwd_done = None
 
     def flush_gradients(self):
@@ -579,7 +579,6 @@ class Trainer:
         accumulated (and reduced) gradient just before the optimizer consumes it (tests, ``bench.py --check-dp``)."""
         if self._coalesced and self._flush_coalesced():
             return                                                        # (the held tiles completed the window: its boundary has run)
-        self.flush_pipeline()
         self.flush_gradients()
         if self.world > 1:
             self.bucket.all_reduce(self.group)                            # one SUM all-reduce per step
@@ -594,14 +593,8 @@ class Trainer:
                 # of its own: the .item() then does not wait for the tile streams' queued work (the collective itself still runs
                 # behind the gradient all-reduce on the process group's internal stream -- one bucket's worth of waiting)
                 dev = self.bucket.flat.device
-                if dev.type == "cuda":
-                    if self._flag_stream is None:
-                        self._flag_stream = torch.cuda.Stream(device=dev)
-                    with torch.cuda.stream(self._flag_stream):
-                        flag = torch.tensor([float(bad)], device=dev)
-                        dist.all_reduce(flag, op=dist.ReduceOp.SUM, group=self.group)
-                        bad = int(flag.item())
-                else:
+                with (torch.cuda.stream(self._lazy_streams("_flag_stream", dev)) if dev.type == "cuda"
+                      else contextlib.nullcontext()):
                     flag = torch.tensor([float(bad)], device=dev)
                     dist.all_reduce(flag, op=dist.ReduceOp.SUM, group=self.group)
                     bad = int(flag.item())
@@ -639,14 +632,9 @@ class Trainer:
     def _reset_accumulators(self):
         self._coalesced = []                               # (error path: tiles accepted but never issued are dropped with the window)
         if self._pending is not None:                      # (error path: a forward whose backward will never be issued)
-            st, data = self._pending[3], self._pending[6]
-            self._hold_inputs(st.record_event(torch.cuda.Event()), data)
+            self._hold_inputs(self._pending.stream.record_event(torch.cuda.Event()), self._pending.data)
         self._pending = None
-        if self._tile_streams is not None:                 # (nothing of the tile pipeline may still be accumulating)
-            cur = torch.cuda.current_stream()
-            for st in self._tile_streams:
-                cur.wait_stream(st)
-        self._bwd_done = None
+        self._join_tile_streams()                          # (nothing of the tile pipeline may still be accumulating)
         if self.compose_cache is not None and self.compose_cache.pending:    # (error path: drop what was accumulated)
             self.compose_cache.drop_accumulated()
         self.accumulated_loss = 0.0
