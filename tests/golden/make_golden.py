@@ -596,7 +596,83 @@ def tile_producer_aug_fixture():
     save("tile_producer_aug", **arrs)
 
 
+def tile_producer_edges_fixture():
+    """(13) the point half of TomoSARDataset.__getitem__ at the edges of its two crops (dataset.py:234-278), composed like (12)
+    from the reference's own crop_pc_2d / invert_transform / apply_transform for every (rot_times, flip_dim):
+      * z in [-30, 80] with a planted global minimum of -33.0 (negative z_shift, as z_bound[0] = -33.7 allows);
+      * points one float64 step inside each window edge: kept by the first crop, cast to 0.0f / 1.0f (or to a tiny positive
+        float32) by the normalisation, so the float32 re-crop of dataset.py:278 decides -- which edge a point meets turns
+        with the augmentation;  points exactly ON each edge (dropped by the first crop);
+      * the z-min point is such a near-edge point: z_shift comes from the FIRST crop (dataset.py:246) whether or not the
+        re-crop keeps the point;  an interior -0.0 beside a +0.0;
+      * `tiny_*`: a second chunk whose only first-crop survivors are near-edge points -- first crop non-empty, re-crop empty
+        for the unaugmented form."""
+    import math
+    import_reference()
+    from utils import crop_pc_2d, invert_transform, apply_transform
+    g = torch.Generator().manual_seed(13)
+    p = 3000
+    chunk = torch.stack([1300.0 + torch.rand(p, generator=g, dtype=torch.float64) * 1000.0,
+                         5400.0 + torch.rand(p, generator=g, dtype=torch.float64) * 1000.0,
+                         -30.0 + torch.rand(p, generator=g, dtype=torch.float64) * 110.0], 1)
+    anchor = torch.tensor([1500.0, 5600.0], dtype=torch.float64)
+    patch_size = torch.tensor([512.0, 512.0], dtype=torch.float64)
+    min_bound, max_bound = anchor, anchor + patch_size
+    (min_x, min_y), (max_x, max_y) = min_bound.tolist(), max_bound.tolist()
+    inf = math.inf
+    near = [(math.nextafter(max_x, -inf), 5800.25), (math.nextafter(min_x, inf), 5900.5),
+            (1700.75, math.nextafter(max_y, -inf)), (1800.125, math.nextafter(min_y, inf)),
+            (math.nextafter(max_x, -inf), math.nextafter(max_y, -inf)), (math.nextafter(min_x, inf), math.nextafter(min_y, inf))]
+    on_edge = [(max_x, 5700.0), (min_x, 5750.0), (1650.0, max_y), (1950.0, min_y)]
+    near_rows = np.array([5, 700, 1401, 2047, 2048, 2998])               # spread over the chunk, both sides of row 2048
+    on_edge_rows = np.array([0, 1, 2049, 2999])
+    zmin_row, zero_rows = 1234, np.array([1500, 1501])
+    for r, (x, y) in zip(near_rows, near):
+        chunk[r, 0], chunk[r, 1] = x, y
+    for r, (x, y) in zip(on_edge_rows, on_edge):
+        chunk[r, 0], chunk[r, 1] = x, y
+    chunk[zmin_row] = torch.tensor([math.nextafter(max_x, -inf), 6000.0, -33.0], dtype=torch.float64)
+    chunk[zero_rows[0]] = torch.tensor([1760.0, 5860.0, -0.0], dtype=torch.float64)
+    chunk[zero_rows[1]] = torch.tensor([1761.0, 5861.0, 0.0], dtype=torch.float64)
+    tiny = torch.tensor([[1400.0, 5800.0, -20.0],                                     # outside
+                         [math.nextafter(max_x, -inf), 5800.0, 5.0],                  # near-edge
+                         [max_x, 5900.0, -25.0],                                      # on the edge: outside
+                         [1700.0, math.nextafter(max_y, -inf), -7.5],                 # near-edge, the first crop's z minimum
+                         [math.nextafter(max_x, -inf), math.nextafter(max_y, -inf), 3.0],
+                         [2500.0, 7000.0, 1.0]], dtype=torch.float64)
+    z_bound = [-33.7, 156.5]
+    scale_mat = torch.diag(torch.tensor([512.0, 512.0, z_bound[1] - z_bound[0], 1], dtype=torch.float64))
+    shift_norm = torch.cat([torch.eye(4, 3, dtype=torch.float64), torch.tensor([0.5, 0.5, 0, 1]).reshape(-1, 1)], 1)
+    rot_mat_dic = {k: (torch.eye(4).double() if k == 0 else _rotation_z(-90.0 * k * math.pi / 180.0)) for k in range(4)}
+    flip_mat_dic = {-1: torch.eye(4).double(), 0: _reflection(0), 1: _reflection(1)}
+    arrs = {"chunk": chunk, "anchor": anchor, "near_rows": np.append(near_rows, zmin_row), "on_edge_rows": on_edge_rows,
+            "zmin_row": np.array([zmin_row]), "zero_rows": zero_rows, "tiny_chunk": tiny, "tiny_near_rows": np.array([1, 3, 4])}
+    for prefix, cloud in (("", chunk), ("tiny_", tiny)):
+        inputs, index = crop_pc_2d(cloud, min_bound, max_bound)                                  # dataset.py:234
+        assert len(inputs) > 0                                                                   # :235
+        z_shift = torch.min(inputs[:, 2]).double().reshape(1)                                    # :246
+        arrs[prefix + "first_index"] = index
+        arrs[prefix + "zshift"] = z_shift
+        for rot_times in range(4):
+            for flip_dim in (-1, 0, 1):
+                tag = f"r{rot_times}_f{flip_dim + 1}"
+                transform_mat = scale_mat.clone()
+                transform_mat[0:3, 3] = torch.cat([(min_bound + max_bound) / 2., z_shift], 0)
+                normalize_mat = shift_norm.double() @ flip_mat_dic[flip_dim].double() @ rot_mat_dic[rot_times].double() \
+                    @ invert_transform(transform_mat).double()                                   # :268-269
+                inputs_norm = apply_transform(inputs, normalize_mat).float()                     # :275-276
+                inputs_norm, index2 = crop_pc_2d(inputs_norm, [0.0, 0.0], [1.0, 1.0])            # :278
+                arrs[f"{prefix}index_{tag}"] = index[index2]
+                arrs[f"{prefix}inputs_{tag}"] = inputs_norm
+    assert float(arrs["zshift"][0]) == -33.0 and float(arrs["tiny_zshift"][0]) == -7.5
+    assert len(arrs["tiny_first_index"]) == 3 and len(arrs["tiny_index_r0_f0"]) == 0
+    save("tile_producer_edges", **arrs)
+
+
 if __name__ == "__main__":
+    if "--only-edges" in sys.argv:
+        tile_producer_edges_fixture()
+        sys.exit(0)
     if "--only-aug" in sys.argv:
         tile_producer_aug_fixture()
         sys.exit(0)
@@ -616,6 +692,7 @@ if __name__ == "__main__":
     if "--only-blend" not in sys.argv:
         tile_producer_fixture()
         tile_producer_aug_fixture()
+        tile_producer_edges_fixture()
     if "--only-blend" not in sys.argv and "--only-producer" not in sys.argv:
         mean_pool_fixture()
         upsample_mode_fixture()

@@ -156,7 +156,8 @@ T2H_API int t2h_tile_crop_normalise_aug(const double *chunk, int64_t P, double m
                                         double scale_x, double scale_y, double scale_z, int rot_times, int flip_dim, float *out,
                                         int32_t *src_index, int32_t *count, double *z_shift, void *workspace,
                                         size_t workspace_bytes, t2h_stream_t stream) {
-    if (!chunk || !out || !count || !z_shift || !workspace) return fail(T2H_ERR_ARG, "tile_crop_normalise: null pointer");
+    // an empty chunk has no storage (a [0, 3] tensor's data pointer is null): chunk may be null when P == 0
+    if ((!chunk && P != 0) || !out || !count || !z_shift || !workspace) return fail(T2H_ERR_ARG, "tile_crop_normalise: null pointer");
     if (rot_times < 0 || rot_times > 3 || flip_dim < -1 || flip_dim > 1) return fail(T2H_ERR_ARG, "tile_crop_normalise: bad augmentation");
     if (P < 0 || P >= ((int64_t)1 << 31) || !(scale_x > 0) || !(scale_y > 0) || !(scale_z > 0))
         return fail(T2H_ERR_ARG, "tile_crop_normalise: bad argument");
