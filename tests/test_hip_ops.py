@@ -31,6 +31,14 @@ def _tile(cloud, reso):
     return TileIndex(cloud.to(_dev()), reso)
 
 
+# Channel counts at which the VEC = 4 / VEC = 1 launcher of the row-streaming kernels takes another shape: 3 and 6 (VEC = 1, fewer
+# lanes than four), 70 (VEC = 1 beyond the 64-lane cap), 20 (VEC = 4, five lanes rounded up to eight), 68 (VEC = 4, no multiple of
+# 64: the VALU per-cell partials), 260 (VEC = 4 beyond the cap) -- each at 257 points on a 4 x 4 grid (16 points per cell: the
+# per-cell partials of the coarse levels are taken) and on a 16 x 16 grid (they are not).
+_EDGE_C = (3, 6, 70, 20, 68, 260)
+_EDGE = [(257, reso, c) for reso in (4, 16) for c in _EDGE_C]
+
+
 @pytest.mark.parametrize("n,reso,batch", [(1, 2, 1), (5, 2, 1), (300, 16, 1), (2049, 64, 2), (70000, 256, 1),
                                           (131072, 256, 1)])
 def test_tile_index_bit_exact(n, reso, batch):
@@ -90,7 +98,8 @@ def _pool_case(cloud, feat, reso, gout):
 
 
 @pytest.mark.parametrize("n,reso,c,batch", [(300, 4, 8, 1), (300, 16, 32, 2), (5000, 64, 32, 1), (777, 16, 12, 1),
-                                            (40000, 256, 32, 1), (3000, 32, 6, 1), (1000, 8, 512, 1)])
+                                            (40000, 256, 32, 1), (3000, 32, 6, 1), (1000, 8, 512, 1)]
+                         + [(n, reso, c, 1) for n, reso, c in _EDGE])
 def test_pool_max_vs_oracle(n, reso, c, batch):
     g = torch.Generator().manual_seed(n + c)
     cloud = synth_cloud(n, seed=n, batch=batch)
@@ -141,7 +150,8 @@ def test_pool_mean_golden():
 
 
 @pytest.mark.parametrize("n,reso,c,batch", [(300, 4, 8, 1), (300, 16, 32, 2), (5000, 64, 32, 1), (777, 16, 12, 1),
-                                            (40000, 256, 32, 1), (3000, 32, 6, 1), (1000, 8, 512, 1)])
+                                            (40000, 256, 32, 1), (3000, 32, 6, 1), (1000, 8, 512, 1)]
+                         + [(n, reso, c, 1) for n, reso, c in _EDGE])
 def test_pool_mean_vs_oracle(n, reso, c, batch):
     from oracle import torch_ref, c_oracle
     g = torch.Generator().manual_seed(n + c)
@@ -159,7 +169,8 @@ def test_pool_mean_vs_oracle(n, reso, c, batch):
 
 @pytest.mark.parametrize("n,reso,c,level,batch", [(257, 4, 8, 0, 1), (257, 16, 8, 0, 1), (257, 32, 12, 0, 1),
                                                   (5000, 64, 32, 0, 2), (5000, 64, 64, 1, 1), (5000, 64, 128, 3, 1),
-                                                  (40000, 256, 32, 0, 1), (20000, 256, 512, 3, 1), (3000, 256, 256, 8, 1)])
+                                                  (40000, 256, 32, 0, 1), (20000, 256, 512, 3, 1), (3000, 256, 256, 8, 1)]
+                         + [(n, reso, c, 0, 1) for n, reso, c in _EDGE])
 def test_rasterise_mean_vs_oracle(n, reso, c, level, batch):
     from tomosar2height_amd import ops
     from oracle import c_oracle
@@ -209,7 +220,8 @@ def test_rasterise_mean_golden():
                                                      (40000, 256, 32, 0, 1, False), (20000, 256, 512, 3, 1, False),
                                                      (3000, 64, 12, 2, 1, False), (2000, 256, 16, 8, 1, False),
                                                      (30000, 256, 128, 1, 2, True), (9000, 256, 64, 0, 1, True),
-                                                     (700, 8, 32, 0, 3, False), (6000, 32, 20, 1, 1, False)])
+                                                     (700, 8, 32, 0, 3, False), (6000, 32, 20, 1, 1, False)]
+                         + [(n, reso, c, 0, 1, False) for n, reso, c in _EDGE])
 def test_sample_plane_vs_oracle(n, reso, c, level, batch, cl):
     from tomosar2height_amd import ops
     from oracle import c_oracle
@@ -239,7 +251,8 @@ def test_sample_plane_vs_oracle(n, reso, c, level, batch, cl):
 
 @pytest.mark.parametrize("n,reso,c,level,batch", [(9000, 256, 64, 0, 1), (30000, 256, 128, 1, 2), (40000, 256, 32, 0, 1),
                                                   (3000, 32, 16, 0, 1), (131072, 256, 64, 0, 1), (300, 8, 64, 0, 3),
-                                                  (5000, 64, 12, 1, 1), (2000, 256, 20, 8, 1), (60000, 256, 256, 2, 1)])
+                                                  (5000, 64, 12, 1, 1), (2000, 256, 20, 8, 1), (60000, 256, 256, 2, 1)]
+                         + [(n, reso, c, 0, 1) for n, reso, c in _EDGE])
 def test_sample_bwd_through_the_transposed_matrix_is_bit_identical_to_the_gather(n, reso, c, level, batch):
     """t2h_sample_adjoint_build + t2h_sample_bwd_adjoint (the CSR of the transposed sampling matrix, cached per tile and
     level) list a pixel's (row, weight) entries in the order the per-pixel gather visits them: identical bits, with and
@@ -275,6 +288,36 @@ def test_sample_bwd_through_the_transposed_matrix_is_bit_identical_to_the_gather
             assert torch.equal(a, b)
         else:
             torch.testing.assert_close(a, b, rtol=1e-4, atol=1e-5 * float(b.abs().max()))     # two orders of summation
+
+
+@pytest.mark.parametrize("n,reso,c", _EDGE)
+def test_sample_bwd_entry_points_vs_oracle(n, reso, c):
+    """t2h_sample_bwd itself (the per-pixel gather, or the per-cell partials + 3 x 3 gather where t2h_sample_bwd_workspace_bytes
+    is not 0) and t2h_sample_bwd_adjoint, each against the oracle with the bound of test_sample_plane_vs_oracle -- whichever of
+    the two ops.sample_plane's backward picks."""
+    from tomosar2height_amd import _lib
+    from oracle import c_oracle
+    g = torch.Generator().manual_seed(n + c)
+    cloud = synth_cloud(n, seed=n + 2)
+    gout = torch.randn(1, n, c, generator=g)
+    t = _tile(cloud, reso)
+    want_g = c_oracle.grid_sample_bwd(gout.numpy(), cloud.numpy(), reso, reso)
+    scale = np.abs(want_g).max() + 1e-6
+    rows = t.sort_rows(gout.to(_dev()))
+    ws_bytes = _lib.load().t2h_sample_bwd_workspace_bytes(1, n, t.nbits, 0, c)
+    assert (ws_bytes > 0) == (c % 4 == 0 and reso == 4)
+    ws = _lib.workspace(ws_bytes, _dev())
+    a = torch.full((1, reso, reso, c), float("nan"), device=_dev())
+    _lib.call("t2h_sample_bwd", _lib.ptr(rows), _lib.ptr(t.pts), t.dim, _lib.ptr(t.off0), 1, n, t.nbits, 0, c, _lib.ptr(a),
+              _lib.ptr(ws), ws_bytes, _lib.stream())
+    offsets, entries = t.sample_adjoint(0)
+    b = torch.full((1, reso, reso, c), float("nan"), device=_dev())
+    _lib.call("t2h_sample_bwd_adjoint", _lib.ptr(rows), _lib.ptr(offsets), _lib.ptr(entries), 1, t.nbits, 0, c, None, _lib.ptr(b),
+              _lib.stream())
+    for got in (a, b):
+        np.testing.assert_allclose(got.permute(0, 3, 1, 2).cpu().numpy(), want_g, rtol=1e-4, atol=1e-5 * scale)
+    if ws_bytes == 0:
+        assert torch.equal(a, b)                                       # the gather and the transposed matrix: the same bits
 
 
 def test_sample_plane_golden():

@@ -45,6 +45,70 @@ def test_ragged_batch_rejects_empty_tiles_and_mixed_dims():
         TileIndex([a, a[..., :2]], 256)
 
 
+@pytest.mark.parametrize("c", [3, 6, 70, 20, 68, 260])
+def test_ragged_point_grid_ops_vs_oracle_tile_by_tile(c):
+    """pool_max, pool_mean, rasterise_mean and sample_plane, forward and backward, on ONE ragged batch of uneven tiles (4 x 4
+    cells, 257 + 40 + 131 rows: about nine rows per cell on average, so t2h_sample_bwd takes its per-cell partials where
+    C % 4 == 0 and the rasteriser its per-cell loop) at the channel counts where the VEC = 4 / VEC = 1 launcher changes
+    shape: every tile against the oracle on that tile alone, with the bounds of the same ops' tests in test_hip_ops.py."""
+    from tomosar2height_amd import _lib, ops
+    from tomosar2height_amd.tile import TileIndex
+    from oracle import c_oracle, torch_ref
+    counts, reso = (257, 40, 131), 4
+    g = torch.Generator().manual_seed(c)
+    clouds = [synth_cloud(n, seed=500 + i) for i, n in enumerate(counts)]
+    rag = TileIndex([x.to(_dev()) for x in clouds], reso)
+    starts = np.concatenate([[0], np.cumsum(counts)])
+    perm = [rag.perm[starts[b]:starts[b + 1]].long().cpu() for b in range(len(counts))]
+    rows = lambda per_tile: torch.cat([x[0][perm[b]] for b, x in enumerate(per_tile)]).contiguous().to(_dev())     # sorted order
+    tile_rows = lambda x, b: x[starts[b]:starts[b + 1]].cpu()[torch.argsort(perm[b])].numpy()[None]                  # cloud order
+    feat = [(torch.randn(1, n, c, generator=g) * 4).round() / 4 for n in counts]
+    gout = [torch.randn(1, n, c, generator=g) for n in counts]
+    plane = torch.randn(len(counts), c, reso, reso, generator=g)
+    gplane = torch.randn(len(counts), c, reso, reso, generator=g)
+    f = rows(feat).requires_grad_(True)
+    grad_of = lambda out, go: torch.autograd.grad(out, f, go)[0]
+    pmax = ops.pool_max(rag, f)
+    pmax_g = grad_of(pmax, rows(gout))
+    pmean = ops.pool_mean(rag, f)
+    pmean_g = grad_of(pmean, rows(gout))
+    rast = ops.rasterise_mean(rag, f, reso)
+    rast_g = grad_of(rast, gplane.to(_dev()))
+    p = plane.to(_dev()).requires_grad_(True)
+    samp = ops.sample_plane(rag, p)
+    samp.backward(rows(gout))
+    # t2h_sample_bwd itself, whichever path ops.sample_plane's backward took
+    ws_bytes = _lib.load().t2h_sample_bwd_workspace_bytes(rag.B, rag.N, rag.nbits, 0, c)
+    assert (ws_bytes > 0) == (c % 4 == 0)
+    ws = _lib.workspace(ws_bytes, _dev())
+    direct = torch.full((len(counts), reso, reso, c), float("nan"), device=_dev())
+    _lib.call("t2h_sample_bwd", _lib.ptr(rows(gout)), _lib.ptr(rag.pts), rag.dim, _lib.ptr(rag.off0), rag.B, rag.N, rag.nbits, 0, c,
+              _lib.ptr(direct), _lib.ptr(ws), ws_bytes, _lib.stream())
+    for b, n in enumerate(counts):
+        cl, idx = clouds[b].numpy(), c_oracle.coordinate2index(clouds[b].numpy(), reso)
+        want, arg = c_oracle.pool_local_fwd(feat[b].numpy(), idx, reso * reso)
+        want_g = c_oracle.pool_local_bwd(gout[b].numpy(), idx, arg, reso * reso)
+        assert np.array_equal(tile_rows(pmax.detach(), b), want)
+        np.testing.assert_allclose(tile_rows(pmax_g, b), want_g, rtol=1e-5, atol=1e-5)
+        assert np.array_equal(tile_rows(pmax_g, b) != 0, want_g != 0)
+        fb = feat[b].clone().requires_grad_(True)
+        want = torch_ref.pool_local(torch.from_numpy(idx), fb, reso, "mean")
+        want.backward(gout[b])
+        assert np.array_equal(tile_rows(pmean.detach(), b), want.detach().numpy())
+        assert np.array_equal(tile_rows(pmean_g, b), fb.grad.numpy())
+        want = c_oracle.scatter_mean_fwd(feat[b].numpy(), idx, reso)
+        np.testing.assert_allclose(rast[b:b + 1].detach().cpu().numpy(), want, rtol=1e-5, atol=1e-6)
+        assert np.array_equal(rast[b:b + 1].detach().cpu().numpy() == 0, want == 0)
+        want_g = c_oracle.scatter_mean_bwd(gplane[b:b + 1].numpy(), idx, n)
+        np.testing.assert_allclose(tile_rows(rast_g, b), want_g, rtol=1e-6, atol=1e-7)
+        want = c_oracle.grid_sample_fwd(plane[b:b + 1].numpy(), cl)
+        np.testing.assert_allclose(tile_rows(samp.detach(), b), want, rtol=1e-5, atol=1e-6)
+        want_g = c_oracle.grid_sample_bwd(gout[b].numpy(), cl, reso, reso)
+        scale = np.abs(want_g).max() + 1e-6
+        np.testing.assert_allclose(p.grad[b:b + 1].cpu().numpy(), want_g, rtol=1e-4, atol=1e-5 * scale)
+        np.testing.assert_allclose(direct[b:b + 1].permute(0, 3, 1, 2).cpu().numpy(), want_g, rtol=1e-4, atol=1e-5 * scale)
+
+
 def _berlin_model(seed=21):
     from tomosar2height_amd import TomoSAR2Height
     from tomosar2height_amd.config import berlin_config

@@ -10,6 +10,7 @@
 // reductions are plain sequential loops over neighbouring rows: no atomics, deterministic sums.
 #include <float.h>
 #include <stdlib.h>
+#include <type_traits>
 
 #include "t2h_common.h"
 
@@ -1725,11 +1726,6 @@ __global__ __launch_bounds__(kThreads) void sample_bwd_atomic_kernel(const float
 
 using namespace t2h;
 
-#define T2H_DISPATCH_VEC(C, CALL4, CALL1) \
-    do {                                  \
-        if ((C) % 4 == 0) { CALL4; } else { CALL1; } \
-    } while (0)
-
 // ---- longest-first dispatch order of a level's cells (t2h_cell_order_build) -------------------------------------------------
 // The on-chip walks give every sampling cell (or 2 x 2 block of cells) its own workgroup, whose duration grows with the cell's
 // row count; workgroups start in blockIdx order, so where a dense cluster sits in the Morton order decides how long the chip
@@ -1789,12 +1785,61 @@ __global__ __launch_bounds__(1024) void cell_order_kernel(const int32_t *__restr
         out[atomicAdd(&hist[kOrderKeys - 1 - min((off0[(c + 1) << shift] - off0[c << shift]) / quantum, kOrderKeys - 1)], 1)] = (int32_t)c;
 }
 
+// ---- host side: shared argument predicates and launchers ----------------------------------------------------------------------
+// (B, nbits, level) name a plane of a batch of tiles (the size functions answer 0 where they do not)
+static bool level_ok(int B, int nbits, int level) {
+    return B >= 1 && nbits >= 1 && nbits <= T2H_MAX_NBITS && level >= 0 && level <= nbits;
+}
 static int check_level(const char *what, int B, int nbits, int level, int C) {
-    if (B < 1 || nbits < 1 || nbits > T2H_MAX_NBITS || level < 0 || level > nbits || C < 1)
+    if (!level_ok(B, nbits, level) || C < 1)
         return fail(T2H_ERR_ARG, "%s: unsupported shape (B=%d nbits=%d level=%d C=%d)", what, B, nbits, level, C);
     return T2H_OK;
 }
+static int check_workspace(const char *what, const void *workspace, size_t workspace_bytes, size_t need) {
+    if (!workspace || workspace_bytes < need) return fail(T2H_ERR_WORKSPACE, "%s: workspace %zu < %zu bytes", what, workspace_bytes, need);
+    return T2H_OK;
+}
+// float4 rows: every pointer given (null passes) is 16-byte aligned and every row stride given (an int, in floats) a multiple of 4
+static bool float4_able(const void *p) { return ((uintptr_t)p & 15) == 0; }
+static bool float4_able(int ld) { return ld % 4 == 0; }
+template <class... A> static bool aligned16(A... a) { return (float4_able(a) && ...); }
 
+// The VEC = 4 (C % 4 == 0: float4 rows) / VEC = 1 dispatch of the row-streaming kernels, `groups` row groups of C channels:
+// launch(vec, lg, grid) gets VEC as a std::integral_constant (kernel<vec()>), log2 of a group's lanes and the grid of kThreads blocks
+template <class Launch>
+static inline void launch_vec(int C, int64_t groups, Launch &&launch) {
+    if (C % 4 == 0) { const int lg = group_cfg<4>(C).lg; launch(std::integral_constant<int, 4>{}, lg, dim3(grid_for(groups, lg))); }
+    else { const int lg = group_cfg<1>(C).lg; launch(std::integral_constant<int, 1>{}, lg, dim3(grid_for(groups, lg))); }
+}
+// t2h_pool_rows_*: kernels instantiated per log2 of a row's lanes (C <= 64 as float4: 0 .. 4); launch(lg, grid of 256-thread blocks)
+template <class Launch>
+static inline void launch_pool_rows(int C, int64_t n_rows, Launch &&launch) {
+    const int lg = group_log2(C, 4);
+    const int rows_per_wg = (256 >> lg) > kPoolRows ? (256 >> lg) : kPoolRows;
+    const dim3 blocks((unsigned)((n_rows + rows_per_wg - 1) / rows_per_wg));
+    if (lg <= 0) launch(std::integral_constant<int, 0>{}, blocks); else if (lg == 1) launch(std::integral_constant<int, 1>{}, blocks);
+    else if (lg == 2) launch(std::integral_constant<int, 2>{}, blocks); else if (lg == 3) launch(std::integral_constant<int, 3>{}, blocks);
+    else launch(std::integral_constant<int, 4>{}, blocks);
+}
+
+// The plane list of t2h_segsum_bwd_multi / t2h_sample_bwd_from_sums into `mp`, checked plane by plane: a plane or level that
+// is not there, rows that are not float4-able (C % 4 == 0), a stride below C (`terse`: "bad plane" for all three); then the
+// caller's own rows (`rows_ok`), then the compact rows.
+static int plane_list(const char *what, bool terse, MultiPlanes &mp, const float *const *planes, const int *levels, const int *lds,
+                      int n_planes, int B, int nbits, int C, bool rows_ok, const int32_t *row_of_cell, int rows_level) {
+    mp.n = n_planes;
+    for (int q = 0; q < n_planes; ++q) {
+        const bool there = planes[q] && levels[q] >= 0 && levels[q] <= nbits, rows4 = C % 4 != 0 || aligned16(planes[q], lds[q]);
+        if (!there || (terse && (!rows4 || lds[q] < C))) return fail(T2H_ERR_ARG, "%s: bad plane %d", what, q);
+        if (!rows4) return fail(T2H_ERR_ARG, "%s: planes must be 16-byte aligned", what);
+        if (lds[q] < C) return fail(T2H_ERR_ARG, "%s: plane %d row stride %d < C", what, q, lds[q]);
+        mp.g[q] = planes[q]; mp.level[q] = levels[q]; mp.ld[q] = lds[q];
+    }
+    if (!rows_ok) return fail(T2H_ERR_ARG, "%s: rows must be 16-byte aligned", what);
+    if (!set_compact(mp, row_of_cell, rows_level, B, nbits))
+        return fail(T2H_ERR_ARG, "%s: compact rows of level %d, which no plane has", what, rows_level);
+    return T2H_OK;
+}
 
 // the matrix-core form of the sample adjoint's per-cell partials: 64-channel wave slices (T2H_CELLS_MFMA=0: the VALU form, A/B)
 static bool cells_mfma(int C) {
@@ -1821,9 +1866,31 @@ static CoarsePlan coarse_plan(int B, int N, int nbits, int level, int C, int min
     p.S = (int)(want < 1 ? 1 : (want > 8 ? 8 : want));
     return p;
 }
+// LDS of the per-cell kernels: P rows x G lanes of float4
+static size_t cells_lds_bytes(const CoarsePlan &cp) { return (size_t)(kCellThreads >> cp.lgG) * (1 << cp.lgG) * sizeof(float4); }
+
+// The sample adjoint's per-cell partials over `cp` (9 slots per cell and split, in `partial`), then the 3 x 3 gather that folds
+// them (+ addend) into the plane.  FUSED: the rows' gradient is formed on the fly from the plane list `mp` under `mask` (float,
+// or BITS: packed sign bits -- matrix-core form only) instead of read from `gout`; tlevel: the matrix-core kernel's table level.
+template <bool FUSED, bool BITS = false>
+static void launch_cells_gather9(const CoarsePlan &cp, const float *gout, const float *pts, int dim, const int32_t *off0, int B, int N,
+                                 int nbits, int level, int C, float *partial, const MultiPlanes &mp, const int32_t *cell,
+                                 const float *mask, int tlevel, const float *addend, float *gplane_nhwc, hipStream_t s) {
+    const int64_t groups = (int64_t)B << (2 * (nbits - level));
+    const dim3 grid((unsigned)groups, cp.S * cp.chunks);
+    if (BITS || cells_mfma(C))
+        hipLaunchKernelGGL((sample_bwd_cells_mfma_kernel<FUSED, BITS>), grid, dim3(kCellThreads), 0, s, gout, pts, dim, off0, nbits, level,
+                           C, cp.S, partial, mp, cell, mask, tlevel, (size_t)rows_of(B, N));
+    else
+        hipLaunchKernelGGL(sample_bwd_cells_kernel<FUSED>, grid, dim3(kCellThreads), cells_lds_bytes(cp), s, gout, pts, dim, off0, nbits,
+                           level, C, cp.lgG, cp.S, partial, mp, cell, mask);
+    const int lg = group_cfg<4>(C).lg;
+    hipLaunchKernelGGL(sample_bwd_gather9_kernel, dim3(grid_for(groups, lg)), dim3(kThreads), 0, s, partial, B, nbits - level, C, lg,
+                       cp.S, addend, gplane_nhwc);
+}
 
 T2H_API size_t t2h_segmean_workspace_bytes(int B, int N, int nbits, int level, int C) {
-    if (B < 1 || nbits < 1 || nbits > T2H_MAX_NBITS || level < 0 || level > nbits || C < 1) return 0;
+    if (!level_ok(B, nbits, level) || C < 1) return 0;
     CoarsePlan p = coarse_plan(B, N, nbits, level, C);
     if (!p.use) return 0;
     return ((size_t)B << (2 * (nbits - level))) * p.S * C * sizeof(float);
@@ -1832,7 +1899,7 @@ T2H_API size_t t2h_segmean_workspace_bytes(int B, int N, int nbits, int level, i
 constexpr int kSampleBwdMinPts = 6;   // the 3x3 gather re-reads rows ~9x: switch to read-once partials early
 
 T2H_API size_t t2h_sample_bwd_workspace_bytes(int B, int N, int nbits, int level, int C) {
-    if (B < 1 || nbits < 1 || nbits > T2H_MAX_NBITS || level < 0 || level > nbits || C < 1) return 0;
+    if (!level_ok(B, nbits, level) || C < 1) return 0;
     CoarsePlan p = coarse_plan(B, N, nbits, level, C, kSampleBwdMinPts);
     if (!p.use) return 0;
     return 9 * ((size_t)B << (2 * (nbits - level))) * p.S * C * sizeof(float);
@@ -1846,19 +1913,14 @@ T2H_API int t2h_pool_max_fwd(const float *feat, int ldf, const int32_t *off0, in
     int rc = check_level("pool_max_fwd", B, nbits, 0, C);
     if (rc) return rc;
     if (ldf < C || ldp < C) return fail(T2H_ERR_ARG, "pool_max_fwd: row stride smaller than C");
-    int64_t ncells = (int64_t)B << (2 * nbits);
-    int ws = t2h_pool_winner_stride(C);
-    bool v4 = C % 4 == 0 && ldf % 4 == 0 && ldp % 4 == 0 && (uintptr_t)feat % 16 == 0 && (uintptr_t)pooled % 16 == 0;
-    if (C % 4 == 0 && !v4) return fail(T2H_ERR_ARG, "pool_max_fwd: rows must be 16-byte aligned when C %% 4 == 0");
-    if (v4) {
-        GroupCfg g = group_cfg<4>(C);
-        hipLaunchKernelGGL(pool_max_fwd_kernel<4>, dim3(grid_for(ncells, g.lg)), dim3(kThreads), 0, as_stream(stream), feat,
-                           off0, ncells, C, ldf, ldp, g.lg, ws, pooled, winner);
-    } else {
-        GroupCfg g = group_cfg<1>(C);
-        hipLaunchKernelGGL(pool_max_fwd_kernel<1>, dim3(grid_for(ncells, g.lg)), dim3(kThreads), 0, as_stream(stream), feat,
-                           off0, ncells, C, ldf, ldp, g.lg, ws, pooled, winner);
-    }
+    if (C % 4 == 0 && !aligned16(feat, pooled, ldf, ldp))
+        return fail(T2H_ERR_ARG, "pool_max_fwd: rows must be 16-byte aligned when C %% 4 == 0");
+    const int64_t ncells = (int64_t)B << (2 * nbits);
+    const int ws = t2h_pool_winner_stride(C);
+    launch_vec(C, ncells, [&](auto vec, int lg, dim3 grid) {
+        hipLaunchKernelGGL(pool_max_fwd_kernel<vec()>, grid, dim3(kThreads), 0, as_stream(stream), feat, off0, ncells, C, ldf, ldp,
+                           lg, ws, pooled, winner);
+    });
     return check_launch("pool_max_fwd");
 }
 
@@ -1868,19 +1930,14 @@ T2H_API int t2h_pool_max_bwd(const float *gpooled, int ldg, const uint8_t *winne
     int rc = check_level("pool_max_bwd", B, nbits, 0, C);
     if (rc) return rc;
     if (ldg < C || ldo < C) return fail(T2H_ERR_ARG, "pool_max_bwd: row stride smaller than C");
-    int64_t ncells = (int64_t)B << (2 * nbits);
-    int ws = t2h_pool_winner_stride(C);
-    bool v4 = C % 4 == 0 && ldg % 4 == 0 && ldo % 4 == 0 && (uintptr_t)gpooled % 16 == 0 && (uintptr_t)gfeat % 16 == 0;
-    if (C % 4 == 0 && !v4) return fail(T2H_ERR_ARG, "pool_max_bwd: rows must be 16-byte aligned when C %% 4 == 0");
-    if (v4) {
-        GroupCfg g = group_cfg<4>(C);
-        hipLaunchKernelGGL(pool_max_bwd_kernel<4>, dim3(grid_for(ncells, g.lg)), dim3(kThreads), 0, as_stream(stream),
-                           gpooled, winner, off0, ncells, C, ldg, ldo, g.lg, ws, accumulate, gfeat);
-    } else {
-        GroupCfg g = group_cfg<1>(C);
-        hipLaunchKernelGGL(pool_max_bwd_kernel<1>, dim3(grid_for(ncells, g.lg)), dim3(kThreads), 0, as_stream(stream),
-                           gpooled, winner, off0, ncells, C, ldg, ldo, g.lg, ws, accumulate, gfeat);
-    }
+    if (C % 4 == 0 && !aligned16(gpooled, gfeat, ldg, ldo))
+        return fail(T2H_ERR_ARG, "pool_max_bwd: rows must be 16-byte aligned when C %% 4 == 0");
+    const int64_t ncells = (int64_t)B << (2 * nbits);
+    const int ws = t2h_pool_winner_stride(C);
+    launch_vec(C, ncells, [&](auto vec, int lg, dim3 grid) {
+        hipLaunchKernelGGL(pool_max_bwd_kernel<vec()>, grid, dim3(kThreads), 0, as_stream(stream), gpooled, winner, off0, ncells, C,
+                           ldg, ldo, lg, ws, accumulate, gfeat);
+    });
     return check_launch("pool_max_bwd");
 }
 
@@ -1891,56 +1948,41 @@ T2H_API int t2h_pool_mean(const float *feat, int ldf, const int32_t *off0, int B
     int rc = check_level("pool_mean", B, nbits, 0, C);
     if (rc) return rc;
     if (ldf < C || ldo < C) return fail(T2H_ERR_ARG, "pool_mean: row stride smaller than C");
-    int64_t ncells = (int64_t)B << (2 * nbits);
-    bool v4 = C % 4 == 0 && ldf % 4 == 0 && ldo % 4 == 0 && (uintptr_t)feat % 16 == 0 && (uintptr_t)out % 16 == 0;
-    if (C % 4 == 0 && !v4) return fail(T2H_ERR_ARG, "pool_mean: rows must be 16-byte aligned when C %% 4 == 0");
-    if (v4) {
-        GroupCfg g = group_cfg<4>(C);
-        hipLaunchKernelGGL(pool_mean_kernel<4>, dim3(grid_for(ncells, g.lg)), dim3(kThreads), 0, as_stream(stream), feat, off0,
-                           ncells, C, ldf, ldo, g.lg, accumulate, out);
-    } else {
-        GroupCfg g = group_cfg<1>(C);
-        hipLaunchKernelGGL(pool_mean_kernel<1>, dim3(grid_for(ncells, g.lg)), dim3(kThreads), 0, as_stream(stream), feat, off0,
-                           ncells, C, ldf, ldo, g.lg, accumulate, out);
-    }
+    if (C % 4 == 0 && !aligned16(feat, out, ldf, ldo))
+        return fail(T2H_ERR_ARG, "pool_mean: rows must be 16-byte aligned when C %% 4 == 0");
+    const int64_t ncells = (int64_t)B << (2 * nbits);
+    launch_vec(C, ncells, [&](auto vec, int lg, dim3 grid) {
+        hipLaunchKernelGGL(pool_mean_kernel<vec()>, grid, dim3(kThreads), 0, as_stream(stream), feat, off0, ncells, C, ldf, ldo, lg,
+                           accumulate, out);
+    });
     return check_launch("pool_mean");
 }
 
 T2H_API int t2h_pool_rows_fwd(const float *feat, int ldf, const int32_t *cell, const int32_t *off0, int64_t n_rows, int C,
                               float *pooled, int ldp, uint8_t *winner, t2h_stream_t stream) {
     if (!feat || !cell || !off0 || !pooled || !winner) return fail(T2H_ERR_ARG, "pool_rows_fwd: null pointer");
-    if (n_rows < 0 || n_rows > (1LL << 30) || C < 4 || C % 4 || C > 64 || ldf < C || ldp < C || ldf % 4 || ldp % 4 ||
-        (uintptr_t)feat % 16 || (uintptr_t)pooled % 16)
+    if (n_rows < 0 || n_rows > (1LL << 30) || C < 4 || C % 4 || C > 64 || ldf < C || ldp < C || !aligned16(feat, pooled, ldf, ldp))
         return fail(T2H_ERR_ARG, "pool_rows_fwd: needs C in {4, 8, .., 64} and 16-byte aligned rows");
     if (n_rows == 0) return T2H_OK;
     const int ws = t2h_pool_winner_stride(C);
-    const int lg = group_log2(C, 4);
-    const int rows_per_wg = (256 >> lg) > kPoolRows ? (256 >> lg) : kPoolRows;
-    const unsigned blocks = (unsigned)((n_rows + rows_per_wg - 1) / rows_per_wg);
-#define T2H_POOL_FWD(LG) hipLaunchKernelGGL(pool_rows_fwd_kernel<LG>, dim3(blocks), dim3(256), 0, as_stream(stream), feat, ldf, \
-                                            cell, off0, (int)n_rows, C, pooled, ldp, winner, ws)
-    if (lg <= 0) T2H_POOL_FWD(0); else if (lg == 1) T2H_POOL_FWD(1); else if (lg == 2) T2H_POOL_FWD(2);
-    else if (lg == 3) T2H_POOL_FWD(3); else T2H_POOL_FWD(4);
-#undef T2H_POOL_FWD
+    launch_pool_rows(C, n_rows, [&](auto lg, dim3 blocks) {
+        hipLaunchKernelGGL(pool_rows_fwd_kernel<lg()>, blocks, dim3(256), 0, as_stream(stream), feat, ldf, cell, off0, (int)n_rows, C,
+                           pooled, ldp, winner, ws);
+    });
     return check_launch("pool_rows_fwd");
 }
 
 T2H_API int t2h_pool_rows_bwd(const float *gpooled, int ldg, const uint8_t *winner, const int32_t *cell, const int32_t *off0,
                               int64_t n_rows, int C, int accumulate, float *gfeat, int ldo, t2h_stream_t stream) {
     if (!gpooled || !winner || !cell || !off0 || !gfeat) return fail(T2H_ERR_ARG, "pool_rows_bwd: null pointer");
-    if (n_rows < 0 || n_rows > (1LL << 30) || C < 4 || C % 4 || C > 64 || ldg < C || ldo < C || ldg % 4 || ldo % 4 ||
-        (uintptr_t)gpooled % 16 || (uintptr_t)gfeat % 16)
+    if (n_rows < 0 || n_rows > (1LL << 30) || C < 4 || C % 4 || C > 64 || ldg < C || ldo < C || !aligned16(gpooled, gfeat, ldg, ldo))
         return fail(T2H_ERR_ARG, "pool_rows_bwd: needs C in {4, 8, .., 64} and 16-byte aligned rows");
     if (n_rows == 0) return T2H_OK;
     const int ws = t2h_pool_winner_stride(C);
-    const int lg = group_log2(C, 4);
-    const int rows_per_wg = (256 >> lg) > kPoolRows ? (256 >> lg) : kPoolRows;
-    const unsigned blocks = (unsigned)((n_rows + rows_per_wg - 1) / rows_per_wg);
-#define T2H_POOL_BWD(LG) hipLaunchKernelGGL(pool_rows_bwd_kernel<LG>, dim3(blocks), dim3(256), 0, as_stream(stream), gpooled, \
-                                            ldg, winner, ws, cell, off0, (int)n_rows, C, accumulate, gfeat, ldo)
-    if (lg <= 0) T2H_POOL_BWD(0); else if (lg == 1) T2H_POOL_BWD(1); else if (lg == 2) T2H_POOL_BWD(2);
-    else if (lg == 3) T2H_POOL_BWD(3); else T2H_POOL_BWD(4);
-#undef T2H_POOL_BWD
+    launch_pool_rows(C, n_rows, [&](auto lg, dim3 blocks) {
+        hipLaunchKernelGGL(pool_rows_bwd_kernel<lg()>, blocks, dim3(256), 0, as_stream(stream), gpooled, ldg, winner, ws, cell, off0,
+                           (int)n_rows, C, accumulate, gfeat, ldo);
+    });
     return check_launch("pool_rows_bwd");
 }
 
@@ -1948,42 +1990,26 @@ static int segreduce_fwd(bool mean, const float *feat, const int32_t *off0, int 
                          float *plane_nhwc, int ld_out, void *workspace, size_t workspace_bytes, t2h_stream_t stream,
                          const int32_t *rowmap = nullptr) {
     if (!feat || !off0 || !plane_nhwc) return fail(T2H_ERR_ARG, "segmean_fwd: null pointer");
-    if (ld_out < C || (C % 4 == 0 && ld_out % 4 != 0)) return fail(T2H_ERR_ARG, "segmean_fwd: plane row stride %d < C = %d", ld_out, C);
+    if (ld_out < C || (C % 4 == 0 && !aligned16(ld_out))) return fail(T2H_ERR_ARG, "segmean_fwd: plane row stride %d < C = %d", ld_out, C);
     int rc = check_level("segmean_fwd", B, nbits, level, C);
     if (rc) return rc;
-    int64_t groups = (int64_t)B << (2 * (nbits - level));
+    const int64_t groups = (int64_t)B << (2 * (nbits - level));
     CoarsePlan cp = coarse_plan(B, N, nbits, level, C);
     if (cp.use) {
-        size_t need = t2h_segmean_workspace_bytes(B, N, nbits, level, C);
-        if (!workspace || workspace_bytes < need)
-            return fail(T2H_ERR_WORKSPACE, "segmean_fwd: workspace %zu < %zu bytes", workspace_bytes, need);
+        rc = check_workspace("segmean_fwd", workspace, workspace_bytes, t2h_segmean_workspace_bytes(B, N, nbits, level, C));
+        if (rc) return rc;
         float *partial = static_cast<float *>(workspace);
-        int G = 1 << cp.lgG, P = kCellThreads >> cp.lgG;
-        hipLaunchKernelGGL(segmean_cells_kernel, dim3((unsigned)groups, cp.S * cp.chunks), dim3(kCellThreads),
-                           (size_t)P * G * sizeof(float4), as_stream(stream), feat, off0, nbits, level, C, cp.lgG, cp.S,
-                           partial);
-        GroupCfg g = group_cfg<4>(C);
-        hipLaunchKernelGGL(segmean_finalize_kernel, dim3(grid_for(groups, g.lg)), dim3(kThreads), 0, as_stream(stream),
-                           partial, off0, B, nbits, level, C, g.lg, cp.S, plane_nhwc, mean ? 1 : 0, ld_out, rowmap);
+        hipLaunchKernelGGL(segmean_cells_kernel, dim3((unsigned)groups, cp.S * cp.chunks), dim3(kCellThreads), cells_lds_bytes(cp),
+                           as_stream(stream), feat, off0, nbits, level, C, cp.lgG, cp.S, partial);
+        const int lg = group_cfg<4>(C).lg;
+        hipLaunchKernelGGL(segmean_finalize_kernel, dim3(grid_for(groups, lg)), dim3(kThreads), 0, as_stream(stream), partial, off0, B,
+                           nbits, level, C, lg, cp.S, plane_nhwc, mean ? 1 : 0, ld_out, rowmap);
         return check_launch("segmean_fwd(coarse)");
     }
-    if (mean) {
-        T2H_DISPATCH_VEC(C,
-            { GroupCfg g = group_cfg<4>(C);
-              hipLaunchKernelGGL(segmean_fwd_kernel<4>, dim3(grid_for(groups, g.lg)), dim3(kThreads), 0, as_stream(stream),
-                                 feat, off0, B, nbits, level, C, g.lg, plane_nhwc, ld_out, rowmap); },
-            { GroupCfg g = group_cfg<1>(C);
-              hipLaunchKernelGGL(segmean_fwd_kernel<1>, dim3(grid_for(groups, g.lg)), dim3(kThreads), 0, as_stream(stream),
-                                 feat, off0, B, nbits, level, C, g.lg, plane_nhwc, ld_out, rowmap); });
-    } else {
-        T2H_DISPATCH_VEC(C,
-            { GroupCfg g = group_cfg<4>(C);
-              hipLaunchKernelGGL((segmean_fwd_kernel<4, false>), dim3(grid_for(groups, g.lg)), dim3(kThreads), 0, as_stream(stream),
-                                 feat, off0, B, nbits, level, C, g.lg, plane_nhwc, ld_out, rowmap); },
-            { GroupCfg g = group_cfg<1>(C);
-              hipLaunchKernelGGL((segmean_fwd_kernel<1, false>), dim3(grid_for(groups, g.lg)), dim3(kThreads), 0, as_stream(stream),
-                                 feat, off0, B, nbits, level, C, g.lg, plane_nhwc, ld_out, rowmap); });
-    }
+    launch_vec(C, groups, [&](auto vec, int lg, dim3 grid) {
+        hipLaunchKernelGGL((mean ? segmean_fwd_kernel<vec(), true> : segmean_fwd_kernel<vec(), false>), grid, dim3(kThreads), 0,
+                           as_stream(stream), feat, off0, B, nbits, level, C, lg, plane_nhwc, ld_out, rowmap);
+    });
     return check_launch("segmean_fwd");
 }
 
@@ -2001,8 +2027,8 @@ T2H_API int t2h_segsum_fwd(const float *feat, const int32_t *off0, int B, int N,
 T2H_API int t2h_plane_sumpool2x2(const float *fine_nhwc, int ld_fine, int B, int r_fine, int C, float *coarse_nhwc, int ld_coarse,
                                  t2h_stream_t stream, const int32_t *fine_row_of_cell) {
     if (!fine_nhwc || !coarse_nhwc) return fail(T2H_ERR_ARG, "plane_sumpool2x2: null pointer");
-    if (B < 1 || r_fine < 2 || (r_fine & 1) || C < 4 || C % 4 != 0 || ((uintptr_t)fine_nhwc & 15) || ((uintptr_t)coarse_nhwc & 15) ||
-        ld_fine < C || ld_coarse < C || ld_fine % 4 != 0 || ld_coarse % 4 != 0)
+    if (B < 1 || r_fine < 2 || (r_fine & 1) || C < 4 || C % 4 != 0 || ld_fine < C || ld_coarse < C ||
+        !aligned16(fine_nhwc, coarse_nhwc, ld_fine, ld_coarse))
         return fail(T2H_ERR_ARG, "plane_sumpool2x2: needs an even resolution, C %% 4 == 0, row strides >= C and 16-byte aligned rows");
     const int rc = r_fine / 2;
     const int64_t total4 = (int64_t)B * rc * rc * (C / 4);
@@ -2018,28 +2044,17 @@ T2H_API int t2h_segsum_bwd_multi(const float *const *gplanes_nhwc, const int *le
     if (!gplanes_nhwc || !levels || !lds || !cell || !gfeat) return fail(T2H_ERR_ARG, "segsum_bwd_multi: null pointer");
     if (n_planes < 1 || n_planes > kMaxMultiPlanes)
         return fail(T2H_ERR_ARG, "segsum_bwd_multi: 1..%d planes, got %d", kMaxMultiPlanes, n_planes);
-    if (B < 1 || nbits < 1 || nbits > T2H_MAX_NBITS || C < 1) return fail(T2H_ERR_ARG, "segsum_bwd_multi: unsupported shape");
+    if (!level_ok(B, nbits, 0) || C < 1) return fail(T2H_ERR_ARG, "segsum_bwd_multi: unsupported shape");
     MultiPlanes mp{};
-    mp.n = n_planes;
-    for (int q = 0; q < n_planes; ++q) {
-        if (!gplanes_nhwc[q] || levels[q] < 0 || levels[q] > nbits) return fail(T2H_ERR_ARG, "segsum_bwd_multi: bad plane %d", q);
-        if (C % 4 == 0 && (((uintptr_t)gplanes_nhwc[q] & 15) || lds[q] % 4 != 0)) return fail(T2H_ERR_ARG, "segsum_bwd_multi: planes must be 16-byte aligned");
-        if (lds[q] < C) return fail(T2H_ERR_ARG, "segsum_bwd_multi: plane %d row stride %d < C", q, lds[q]);
-        mp.g[q] = gplanes_nhwc[q]; mp.level[q] = levels[q]; mp.ld[q] = lds[q];
-    }
-    if (C % 4 == 0 && ((mask && ((uintptr_t)mask & 15)) || (addend && ((uintptr_t)addend & 15)) || ((uintptr_t)gfeat & 15)))
-        return fail(T2H_ERR_ARG, "segsum_bwd_multi: rows must be 16-byte aligned");
-    if (!set_compact(mp, row_of_cell, rows_level, B, nbits))
-        return fail(T2H_ERR_ARG, "segsum_bwd_multi: compact rows of level %d, which no plane has", rows_level);
+    int rc = plane_list("segsum_bwd_multi", false, mp, gplanes_nhwc, levels, lds, n_planes, B, nbits, C,
+                        C % 4 != 0 || aligned16(mask, addend, gfeat), row_of_cell, rows_level);
+    if (rc) return rc;
     const int64_t npts = rows_of(B, N);
     if (npts == 0) return T2H_OK;
-    T2H_DISPATCH_VEC(C,
-        { GroupCfg g = group_cfg<4>(C);
-          hipLaunchKernelGGL(segsum_bwd_multi_kernel<4>, dim3(grid_for(npts, g.lg)), dim3(kThreads), 0, as_stream(stream),
-                             mp, cell, npts, nbits, C, g.lg, mask, addend, gfeat); },
-        { GroupCfg g = group_cfg<1>(C);
-          hipLaunchKernelGGL(segsum_bwd_multi_kernel<1>, dim3(grid_for(npts, g.lg)), dim3(kThreads), 0, as_stream(stream),
-                             mp, cell, npts, nbits, C, g.lg, mask, addend, gfeat); });
+    launch_vec(C, npts, [&](auto vec, int lg, dim3 grid) {
+        hipLaunchKernelGGL(segsum_bwd_multi_kernel<vec()>, grid, dim3(kThreads), 0, as_stream(stream), mp, cell, npts, nbits, C, lg,
+                           mask, addend, gfeat);
+    });
     return check_launch("segsum_bwd_multi");
 }
 
@@ -2051,18 +2066,15 @@ T2H_API int t2h_segmean_bwd(const float *gplane_nhwc, const int32_t *cell, const
 T2H_API int t2h_segmean_bwd_add(const float *gplane_nhwc, const int32_t *cell, const int32_t *off0, int B, int N, int nbits,
                                 int level, int C, const float *addend, float *gfeat, t2h_stream_t stream) {
     if (!gplane_nhwc || !cell || !off0 || !gfeat) return fail(T2H_ERR_ARG, "segmean_bwd: null pointer");
-    if (addend && C % 4 == 0 && ((uintptr_t)addend & 15)) return fail(T2H_ERR_ARG, "segmean_bwd: addend must be 16-byte aligned");
+    if (C % 4 == 0 && !aligned16(addend)) return fail(T2H_ERR_ARG, "segmean_bwd: addend must be 16-byte aligned");
     int rc = check_level("segmean_bwd", B, nbits, level, C);
     if (rc) return rc;
-    int64_t npts = rows_of(B, N);
+    const int64_t npts = rows_of(B, N);
     if (npts == 0) return T2H_OK;
-    T2H_DISPATCH_VEC(C,
-        { GroupCfg g = group_cfg<4>(C);
-          hipLaunchKernelGGL(segmean_bwd_kernel<4>, dim3(grid_for(npts, g.lg)), dim3(kThreads), 0, as_stream(stream),
-                             gplane_nhwc, cell, off0, npts, nbits, level, C, g.lg, addend, gfeat); },
-        { GroupCfg g = group_cfg<1>(C);
-          hipLaunchKernelGGL(segmean_bwd_kernel<1>, dim3(grid_for(npts, g.lg)), dim3(kThreads), 0, as_stream(stream),
-                             gplane_nhwc, cell, off0, npts, nbits, level, C, g.lg, addend, gfeat); });
+    launch_vec(C, npts, [&](auto vec, int lg, dim3 grid) {
+        hipLaunchKernelGGL(segmean_bwd_kernel<vec()>, grid, dim3(kThreads), 0, as_stream(stream), gplane_nhwc, cell, off0, npts, nbits,
+                           level, C, lg, addend, gfeat);
+    });
     return check_launch("segmean_bwd");
 }
 
@@ -2070,20 +2082,17 @@ T2H_API int t2h_sample_fwd(const float *plane_nhwc, const float *pts, int dim, i
                            t2h_stream_t stream) {
     if (!plane_nhwc || !pts || !out) return fail(T2H_ERR_ARG, "sample_fwd: null pointer");
     if (dim < 2 || B < 1 || r < 1 || C < 1 || (N < 0 && dim < 3)) return fail(T2H_ERR_ARG, "sample_fwd: unsupported shape");
-    int64_t npts = rows_of(B, N);
+    const int64_t npts = rows_of(B, N);
     if (npts == 0) return T2H_OK;
-    T2H_DISPATCH_VEC(C,
-        { GroupCfg g = group_cfg<4>(C);
-          hipLaunchKernelGGL(sample_fwd_kernel<4>, dim3(grid_for(npts, g.lg)), dim3(kThreads), 0, as_stream(stream),
-                             plane_nhwc, pts, dim, npts, N, r, C, g.lg, out); },
-        { GroupCfg g = group_cfg<1>(C);
-          hipLaunchKernelGGL(sample_fwd_kernel<1>, dim3(grid_for(npts, g.lg)), dim3(kThreads), 0, as_stream(stream),
-                             plane_nhwc, pts, dim, npts, N, r, C, g.lg, out); });
+    launch_vec(C, npts, [&](auto vec, int lg, dim3 grid) {
+        hipLaunchKernelGGL(sample_fwd_kernel<vec()>, grid, dim3(kThreads), 0, as_stream(stream), plane_nhwc, pts, dim, npts, N, r, C,
+                           lg, out);
+    });
     return check_launch("sample_fwd");
 }
 
 T2H_API size_t t2h_cell_order_len(int B, int nbits, int level) {
-    if (B < 1 || nbits < 1 || nbits > T2H_MAX_NBITS || level < 0 || level >= nbits) return 0;
+    if (!level_ok(B, nbits, level) || level == nbits) return 0;
     const size_t cells = (size_t)B << (2 * (nbits - level));
     return cells + (cells >> 2);
 }
@@ -2122,12 +2131,12 @@ T2H_API int t2h_sample_relu_cellsums_ordered(const float *plane_nhwc, const floa
                                              float *pooled_nhwc, int ld_pooled, void *sign_bits, const int32_t *cell_order,
                                              t2h_stream_t stream, const int32_t *row_of_cell) {
     if (!plane_nhwc || !pts || !off0 || !sums_nhwc) return fail(T2H_ERR_ARG, "sample_relu_cellsums: null pointer");
-    if (pooled_nhwc && (sum_level >= level || ld_pooled < C || ld_pooled % 4 != 0 || ((uintptr_t)pooled_nhwc & 15)))
+    if (pooled_nhwc && (sum_level >= level || ld_pooled < C || !aligned16(pooled_nhwc, ld_pooled)))
         return fail(T2H_ERR_ARG, "sample_relu_cellsums: the pooled sums need sum_level < level and 16-byte aligned rows of >= C floats");
     int rc = check_level("sample_relu_cellsums", B, nbits, level, C);
     if (rc) return rc;
-    if (dim < 2 || sum_level < 0 || sum_level > level || C % 256 != 0 || ld_sums < C || ld_sums % 4 != 0 ||
-        ((uintptr_t)plane_nhwc & 15) || ((uintptr_t)sums_nhwc & 15) || ((uintptr_t)sign_bits & 15))
+    if (dim < 2 || sum_level < 0 || sum_level > level || C % 256 != 0 || ld_sums < C ||
+        !aligned16(plane_nhwc, sums_nhwc, sign_bits, ld_sums))
         return fail(T2H_ERR_ARG, "sample_relu_cellsums: needs C %% 256 == 0, sum_level <= level, 16-byte aligned rows");
     if (rows_of(B, N) == 0) return fail(T2H_ERR_ARG, "sample_relu_cellsums: empty tile");
     // K = 1 stages a 2 x 2 block of sampling cells: the 1 x 1 plane of level == nbits has none (t2h_cell_order_len is 0 there)
@@ -2174,7 +2183,7 @@ T2H_API int t2h_sample_bwd_from_sums_ordered(const float *const *gplanes_nhwc, c
         return fail(T2H_ERR_ARG, "sample_bwd_from_sums: 1..%d planes, got %d", kMaxMultiPlanes, n_planes);
     int rc = check_level("sample_bwd_from_sums", B, nbits, level, C);
     if (rc) return rc;
-    if (dim < 2 || C % 4 != 0 || ((uintptr_t)mask & 15)) return fail(T2H_ERR_ARG, "sample_bwd_from_sums: unsupported shape");
+    if (dim < 2 || C % 4 != 0 || !aligned16(mask)) return fail(T2H_ERR_ARG, "sample_bwd_from_sums: unsupported shape");
     if (mask_is_bits && (C % 256 != 0 || !cells_mfma(C)))
         return fail(T2H_ERR_ARG, "sample_bwd_from_sums: packed sign bits need C %% 256 == 0 (and the matrix-core partials)");
     const float *maskf = static_cast<const float *>(mask);
@@ -2182,21 +2191,13 @@ T2H_API int t2h_sample_bwd_from_sums_ordered(const float *const *gplanes_nhwc, c
     if (!cp.use)
         return fail(T2H_ERR_ARG, "sample_bwd_from_sums: level %d holds too few points per cell for the per-cell partials "
                                  "(t2h_sample_bwd_workspace_bytes == 0): use t2h_segsum_bwd_multi + t2h_sample_bwd", level);
-    size_t need = t2h_sample_bwd_workspace_bytes(B, N, nbits, level, C);
-    if (!workspace || workspace_bytes < need)
-        return fail(T2H_ERR_WORKSPACE, "sample_bwd_from_sums: workspace %zu < %zu bytes", workspace_bytes, need);
+    rc = check_workspace("sample_bwd_from_sums", workspace, workspace_bytes, t2h_sample_bwd_workspace_bytes(B, N, nbits, level, C));
+    if (rc) return rc;
     MultiPlanes mp{};
-    mp.n = n_planes;
-    for (int q = 0; q < n_planes; ++q) {
-        if (!gplanes_nhwc[q] || levels[q] < 0 || levels[q] > nbits || ((uintptr_t)gplanes_nhwc[q] & 15) || lds[q] < C || lds[q] % 4)
-            return fail(T2H_ERR_ARG, "sample_bwd_from_sums: bad plane %d", q);
-        mp.g[q] = gplanes_nhwc[q]; mp.level[q] = levels[q]; mp.ld[q] = lds[q];
-    }
-    if (!set_compact(mp, row_of_cell, rows_level, B, nbits))
-        return fail(T2H_ERR_ARG, "sample_bwd_from_sums: compact rows of level %d, which no plane has", rows_level);
+    rc = plane_list("sample_bwd_from_sums", true, mp, gplanes_nhwc, levels, lds, n_planes, B, nbits, C, true, row_of_cell, rows_level);
+    if (rc) return rc;
     int64_t groups = (int64_t)B << (2 * (nbits - level));
     float *partial = static_cast<float *>(workspace);
-    int G = 1 << cp.lgG, P = kCellThreads >> cp.lgG;
     // table level of the matrix-core kernel: two levels finer than the sampling level (16 entries), not finer than the
     // finest plane; -1 (no table) when no plane would go into it or the rows per workgroup would not repay building it
     static const int table_on = (int)env_ll("T2H_CELLS_TABLE", 1);
@@ -2238,18 +2239,11 @@ T2H_API int t2h_sample_bwd_from_sums_ordered(const float *const *gplanes_nhwc, c
         return check_launch("sample_bwd_from_sums(walk)");
     }
     if (mask_is_bits)
-        hipLaunchKernelGGL((sample_bwd_cells_mfma_kernel<true, true>), dim3((unsigned)groups, cp.S * cp.chunks), dim3(kCellThreads), 0,
-                           as_stream(stream), nullptr, pts, dim, off0, nbits, level, C, cp.S, partial, mp, cell, maskf, tlevel, (size_t)rows_of(B, N));
-    else if (cells_mfma(C))
-        hipLaunchKernelGGL(sample_bwd_cells_mfma_kernel<true>, dim3((unsigned)groups, cp.S * cp.chunks), dim3(kCellThreads), 0,
-                           as_stream(stream), nullptr, pts, dim, off0, nbits, level, C, cp.S, partial, mp, cell, maskf, tlevel, (size_t)rows_of(B, N));
+        launch_cells_gather9<true, true>(cp, nullptr, pts, dim, off0, B, N, nbits, level, C, partial, mp, cell, maskf, tlevel, nullptr,
+                                         gplane_nhwc, as_stream(stream));
     else
-        hipLaunchKernelGGL(sample_bwd_cells_kernel<true>, dim3((unsigned)groups, cp.S * cp.chunks), dim3(kCellThreads),
-                           (size_t)P * G * sizeof(float4), as_stream(stream), nullptr, pts, dim, off0, nbits, level, C, cp.lgG, cp.S,
-                           partial, mp, cell, maskf);
-    GroupCfg g = group_cfg<4>(C);
-    hipLaunchKernelGGL(sample_bwd_gather9_kernel, dim3(grid_for(groups, g.lg)), dim3(kThreads), 0, as_stream(stream),
-                       partial, B, nbits - level, C, g.lg, cp.S, nullptr, gplane_nhwc);
+        launch_cells_gather9<true>(cp, nullptr, pts, dim, off0, B, N, nbits, level, C, partial, mp, cell, maskf, tlevel, nullptr,
+                                   gplane_nhwc, as_stream(stream));
     return check_launch("sample_bwd_from_sums");
 }
 
@@ -2257,17 +2251,14 @@ T2H_API int t2h_sample_fwd_relu(const float *plane_nhwc, const float *pts, int d
                                 void *sign_bits, t2h_stream_t stream) {
     if (!plane_nhwc || !pts || !out) return fail(T2H_ERR_ARG, "sample_fwd_relu: null pointer");
     if (dim < 2 || B < 1 || r < 1 || C < 1 || (N < 0 && dim < 3)) return fail(T2H_ERR_ARG, "sample_fwd_relu: unsupported shape");
-    if (sign_bits && (C % 256 != 0 || ((uintptr_t)sign_bits & 15)))
+    if (sign_bits && (C % 256 != 0 || !aligned16(sign_bits)))
         return fail(T2H_ERR_ARG, "sample_fwd_relu: the packed sign bits need C %% 256 == 0 and a 16-byte aligned buffer");
-    int64_t npts = rows_of(B, N);
+    const int64_t npts = rows_of(B, N);
     if (npts == 0) return T2H_OK;
-    T2H_DISPATCH_VEC(C,
-        { GroupCfg g = group_cfg<4>(C);
-          hipLaunchKernelGGL((sample_fwd_kernel<4, true>), dim3(grid_for(npts, g.lg)), dim3(kThreads), 0, as_stream(stream),
-                             plane_nhwc, pts, dim, npts, N, r, C, g.lg, out, static_cast<unsigned long long *>(sign_bits)); },
-        { GroupCfg g = group_cfg<1>(C);
-          hipLaunchKernelGGL((sample_fwd_kernel<1, true>), dim3(grid_for(npts, g.lg)), dim3(kThreads), 0, as_stream(stream),
-                             plane_nhwc, pts, dim, npts, N, r, C, g.lg, out); });
+    launch_vec(C, npts, [&](auto vec, int lg, dim3 grid) {          // the sign bits: VEC = 4 only
+        hipLaunchKernelGGL((sample_fwd_kernel<vec(), true>), grid, dim3(kThreads), 0, as_stream(stream), plane_nhwc, pts, dim, npts, N, r,
+                           C, lg, out, vec() == 4 ? static_cast<unsigned long long *>(sign_bits) : nullptr);
+    });
     return check_launch("sample_fwd_relu");
 }
 
@@ -2281,43 +2272,27 @@ T2H_API int t2h_sample_bwd_add(const float *gout, const float *pts, int dim, con
                                int level, int C, const float *addend, float *gplane_nhwc, void *workspace,
                                size_t workspace_bytes, t2h_stream_t stream) {
     if (!gout || !pts || !off0 || !gplane_nhwc) return fail(T2H_ERR_ARG, "sample_bwd: null pointer");
-    if (addend && ((uintptr_t)addend & 15)) return fail(T2H_ERR_ARG, "sample_bwd: addend must be 16-byte aligned");
+    if (!aligned16(addend)) return fail(T2H_ERR_ARG, "sample_bwd: addend must be 16-byte aligned");
     int rc = check_level("sample_bwd", B, nbits, level, C);
     if (rc) return rc;
     if (dim < 2) return fail(T2H_ERR_ARG, "sample_bwd: unsupported shape");
-    int64_t groups = (int64_t)B << (2 * (nbits - level));
     CoarsePlan cp = coarse_plan(B, N, nbits, level, C, kSampleBwdMinPts);
     if (cp.use) {
-        size_t need = t2h_sample_bwd_workspace_bytes(B, N, nbits, level, C);
-        if (!workspace || workspace_bytes < need)
-            return fail(T2H_ERR_WORKSPACE, "sample_bwd: workspace %zu < %zu bytes", workspace_bytes, need);
-        float *partial = static_cast<float *>(workspace);
-        int G = 1 << cp.lgG, P = kCellThreads >> cp.lgG;
-        if (cells_mfma(C))
-            hipLaunchKernelGGL(sample_bwd_cells_mfma_kernel<false>, dim3((unsigned)groups, cp.S * cp.chunks), dim3(kCellThreads), 0,
-                               as_stream(stream), gout, pts, dim, off0, nbits, level, C, cp.S, partial, MultiPlanes{}, nullptr,
-                               nullptr, -1, (size_t)rows_of(B, N));
-        else
-            hipLaunchKernelGGL(sample_bwd_cells_kernel<false>, dim3((unsigned)groups, cp.S * cp.chunks), dim3(kCellThreads),
-                               (size_t)P * G * sizeof(float4), as_stream(stream), gout, pts, dim, off0, nbits, level, C,
-                               cp.lgG, cp.S, partial, MultiPlanes{}, nullptr, nullptr);
-        GroupCfg g = group_cfg<4>(C);
-        hipLaunchKernelGGL(sample_bwd_gather9_kernel, dim3(grid_for(groups, g.lg)), dim3(kThreads), 0, as_stream(stream),
-                           partial, B, nbits - level, C, g.lg, cp.S, addend, gplane_nhwc);
+        rc = check_workspace("sample_bwd", workspace, workspace_bytes, t2h_sample_bwd_workspace_bytes(B, N, nbits, level, C));
+        if (rc) return rc;
+        launch_cells_gather9<false>(cp, gout, pts, dim, off0, B, N, nbits, level, C, static_cast<float *>(workspace), MultiPlanes{},
+                                    nullptr, nullptr, -1, addend, gplane_nhwc, as_stream(stream));
         return check_launch("sample_bwd(coarse)");
     }
-    T2H_DISPATCH_VEC(C,
-        { GroupCfg g = group_cfg<4>(C);
-          hipLaunchKernelGGL(sample_bwd_kernel<4>, dim3(grid_for(groups, g.lg)), dim3(kThreads), 0, as_stream(stream),
-                             gout, pts, dim, off0, B, nbits, level, C, g.lg, addend, gplane_nhwc); },
-        { GroupCfg g = group_cfg<1>(C);
-          hipLaunchKernelGGL(sample_bwd_kernel<1>, dim3(grid_for(groups, g.lg)), dim3(kThreads), 0, as_stream(stream),
-                             gout, pts, dim, off0, B, nbits, level, C, g.lg, addend, gplane_nhwc); });
+    launch_vec(C, (int64_t)B << (2 * (nbits - level)), [&](auto vec, int lg, dim3 grid) {
+        hipLaunchKernelGGL(sample_bwd_kernel<vec()>, grid, dim3(kThreads), 0, as_stream(stream), gout, pts, dim, off0, B, nbits, level,
+                           C, lg, addend, gplane_nhwc);
+    });
     return check_launch("sample_bwd");
 }
 
 T2H_API size_t t2h_sample_adjoint_offsets_len(int B, int nbits, int level) {
-    if (B < 1 || nbits < 1 || nbits > T2H_MAX_NBITS || level < 0 || level > nbits) return 0;
+    if (!level_ok(B, nbits, level)) return 0;
     const int64_t npix = (int64_t)B << (2 * (nbits - level));
     return (size_t)(npix + 1 + (npix + 15) / 16 + 1);
 }
@@ -2344,18 +2319,15 @@ T2H_API int t2h_sample_adjoint_build(const float *pts, int dim, const int32_t *o
 T2H_API int t2h_sample_bwd_adjoint(const float *gout, const int32_t *offsets, const void *entries, int B, int nbits, int level,
                                    int C, const float *addend, float *gplane_nhwc, t2h_stream_t stream) {
     if (!gout || !offsets || !entries || !gplane_nhwc) return fail(T2H_ERR_ARG, "sample_bwd_adjoint: null pointer");
-    if (addend && ((uintptr_t)addend & 15)) return fail(T2H_ERR_ARG, "sample_bwd_adjoint: addend must be 16-byte aligned");
+    if (!aligned16(addend)) return fail(T2H_ERR_ARG, "sample_bwd_adjoint: addend must be 16-byte aligned");
     int rc = check_level("sample_bwd_adjoint", B, nbits, level, C);
     if (rc) return rc;
     const int rbits = nbits - level;
     const int64_t npix = (int64_t)B << (2 * rbits);
-    T2H_DISPATCH_VEC(C,
-        { GroupCfg g = group_cfg<4>(C);
-          hipLaunchKernelGGL(sample_bwd_adjoint_kernel<4>, dim3(grid_for(npix, g.lg)), dim3(kThreads), 0, as_stream(stream), gout,
-                             offsets, static_cast<const int2 *>(entries), npix, rbits, C, g.lg, addend, gplane_nhwc); },
-        { GroupCfg g = group_cfg<1>(C);
-          hipLaunchKernelGGL(sample_bwd_adjoint_kernel<1>, dim3(grid_for(npix, g.lg)), dim3(kThreads), 0, as_stream(stream), gout,
-                             offsets, static_cast<const int2 *>(entries), npix, rbits, C, g.lg, addend, gplane_nhwc); });
+    launch_vec(C, npix, [&](auto vec, int lg, dim3 grid) {
+        hipLaunchKernelGGL(sample_bwd_adjoint_kernel<vec()>, grid, dim3(kThreads), 0, as_stream(stream), gout, offsets,
+                           static_cast<const int2 *>(entries), npix, rbits, C, lg, addend, gplane_nhwc);
+    });
     return check_launch("sample_bwd_adjoint");
 }
 
