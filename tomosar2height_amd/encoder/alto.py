@@ -78,7 +78,8 @@ class _PointGridLevel(nn.Module):
         if self.sample_mode != "bilinear":
             # r06: 'bicubic' / 'nearest' (alto.py:95,204; no shipped config, and the reference's own U-Net never passes the
             # argument on -- only a directly constructed level can carry it): the plain sample -> MLP -> rasterise on the
-            # mode's own kernels (csrc/bicubic.hip); the re-associated forms below rest on the bilinear kernels
+            # mode's own kernels (csrc/bicubic.hip; a ragged batch on t2h_sample_rows_*, whose adjoint is a deterministic gather,
+            # a regular one on the atomic adjoint); the re-associated forms below rest on the bilinear kernels
             if isinstance(c_last, deferred.Deferred):
                 raise NotImplementedError("a level with sample_mode != 'bilinear' after a deferred level: construct the whole "
                                           "U-Net's levels with the same mode (UNet.forward_sorted then defers nothing)")

@@ -453,10 +453,49 @@ class _SampleBicubic(torch.autograd.Function):
         return gplane, None, None
 
 
+_ROW_MODES = {"nearest": 0, "bicubic": 1}
+
+
+class _SampleRows(torch.autograd.Function):
+    """The same two samplers on the sorted rows of a tile index, regular or ragged (``t2h_sample_rows_fwd`` / ``_bwd``): plane
+    [B, C, r, r] -> [rows, C].  The forward keeps nothing but the index; the backward is a gather in a fixed order (no atomics,
+    bit-reproducible) and returns the plane gradient in the plane's layout."""
+
+    @staticmethod
+    def forward(ctx, plane, tile: TileIndex, mode: str):
+        plane, cl = _plane_layout(_f32(plane, "sample_plane_mode"))
+        b, c, r, r2 = plane.shape
+        if r != r2 or b != tile.B:
+            raise ValueError(f"sample_plane_mode: expected [B={tile.B}, C, r, r], got {tuple(plane.shape)}")
+        tile.level(r)                                              # a power of two, no finer than the tile's resolution
+        rows = tile.n_points
+        out = torch.empty(rows, c, dtype=torch.float32, device=plane.device)
+        _lib.call("t2h_sample_rows_fwd", _lib.ptr(plane), _lib.ptr(tile.pts), tile.dim, _lib.ptr(tile.off0), tile.B, tile.N,
+                  tile.nbits, r, c, cl, _ROW_MODES[mode], _lib.ptr(out), _lib.stream(),
+                  nbytes=4 * c * rows + 4 * tile.pts.numel() + 4 * plane.numel())
+        ctx.tile, ctx.meta = tile, (b, c, r, cl, mode)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        tile = ctx.tile
+        b, c, r, cl, mode = ctx.meta
+        gout = gout.contiguous()
+        gplane = _empty_like_layout(b, c, r, r, cl, gout.device)
+        _lib.call("t2h_sample_rows_bwd", _lib.ptr(gout), _lib.ptr(tile.pts), tile.dim, _lib.ptr(tile.off0), tile.B, tile.N,
+                  tile.nbits, r, c, cl, _ROW_MODES[mode], gplane.data_ptr(), _lib.stream(),
+                  nbytes=4 * c * tile.n_points + 4 * tile.pts.numel() + 4 * gplane.numel())
+        return gplane, None, None
+
+
 def sample_plane_mode(tile: TileIndex, plane: torch.Tensor, mode: str) -> torch.Tensor:
-    """alto.py:90-95 with sample_mode='bicubic' / 'nearest' on the tile's sorted rows -> [rows, C] (regular batches only)."""
-    if tile.pts.shape[0] != tile.B * tile.N:
-        raise NotImplementedError(f"sample_mode={mode!r} is built for regular [B, N, 3] batches only")
+    """alto.py:90-95 with sample_mode='bicubic' / 'nearest' on the tile's sorted rows -> [rows, C].  A ragged tile (a list of
+    clouds in one index) runs on ``t2h_sample_rows_*``, whose adjoint is a deterministic gather; a regular [B, N, 3] batch keeps
+    ``t2h_sample_{bicubic,nearest}_*`` with their atomic adjoint (its results are pinned by fixtures)."""
+    if mode not in _ROW_MODES:
+        raise ValueError(f"sample_plane_mode: mode must be 'bicubic' or 'nearest', got {mode!r}")
+    if tile.ragged:
+        return _SampleRows.apply(plane, tile, mode)
     pts = tile.pts.view(tile.B, tile.N, tile.pts.shape[1])
     return _SampleBicubic.apply(plane, pts, mode).reshape(-1, plane.shape[1])
 
