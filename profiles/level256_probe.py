@@ -53,3 +53,11 @@ for B in (1, 4):
         us = timed(fn)
         print(f"B = {B}  {name:22s} {us:9.1f} us = {us / B:8.1f} us per tile   {nbytes / us / 1e6:6.2f} TB/s   "
               f"{2.0 * M * N * K / us / 1e6:7.1f} TF")
+    # r08: the two row-wise products on a compact matrix (a device row count, deferred.py) -- does their time follow the rows in use?
+    # 0.69: the occupied share of the r = 256 cells in bench.py's default cloud
+    for frac in (1.0, 0.69, 0.5):
+        lim = torch.tensor([int(frac * M)], dtype=torch.int32, device=dev)
+        for name, fn in (("forward  Y = X W^T", lambda: mlp.linear_fwd_(x, w, None, y, bx3=True, row_limit=lim.data_ptr())),
+                         ("dgrad    dX = dY W", lambda: mlp.linear_dgrad_(dy, w, dx, bx3=True, row_limit=lim.data_ptr()))):
+            us = timed(fn)
+            print(f"B = {B}  {name:22s} rows in use {frac:4.2f}  {us:9.1f} us   {frac * nbytes / us / 1e6:6.2f} TB/s over the rows in use")

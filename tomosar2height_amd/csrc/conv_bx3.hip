@@ -268,8 +268,8 @@ struct RowsArgs {
     // a decoder activation's gradient (pixel.py:31: conv4(cat[x, x1, x2, x3])), formed in this epilogue instead of being written by
     // the head's backward and read back here as "old values" (T2H_ACCUM): same products, same order of additions, same bits
     const float *r1_g, *r1_w;
-    // plain 1-tap (GEMM) form on a compact matrix (T2H_COMPACT_SUMS): device int, the rows in use.  A workgroup whose first row lies
-    // behind them returns; the last partial tile stages the rows behind them as ZEROS (they are uninitialised memory, and a staged
+    // plain 1-tap (GEMM) form on a compact matrix (T2H_COMPACT_SUMS): device int, the rows in use.  The workgroups are ordered over
+    // the row tiles in use (the first ones of the dense grid take them, the others return); the last partial tile stages the rows behind them as ZEROS (they are uninitialised memory, and a staged
     // value takes part in the tile's fp16 block scale), and what it computes for them nobody reads
     const int *row_limit;
 };
@@ -324,12 +324,27 @@ __global__ __launch_bounds__(NT, 2) void bx3_rows_kernel(RowsArgs p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WAVES_N, wn = wave % WAVES_N;
     // XCD-aware order: a contiguous run of tiles per XCD (neighbouring tiles share halo pixels and all share the weights in L2)
-    const unsigned nb = gridDim.x, bid = blockIdx.x;
+    unsigned nb = gridDim.x;
+    const unsigned bid = blockIdx.x;
+    const int ntn = p.Nc / BN;
+    const int tn_groups = PERSIST ? (ntn + p.ntn_per_wg - 1) / p.ntn_per_wg : ntn;
+    int row_lim = 0x7fffffff;
+    if (NTAP == 1 && UPM == 0 && p.row_limit) {                          // read once per workgroup into an SGPR
+        row_lim = __builtin_amdgcn_readfirstlane(*p.row_limit);
+        // r08: the order runs over the row tiles IN USE.  The grid is sized for the dense matrix; ordered over that, the XCDs that
+        // own the tail of the tile range got nothing but workgroups that return, and the others carried all the rows (31 % empty
+        // cells at r = 256: 5.5 of 8 XCDs at work).  Which workgroup computes a tile changes, no tile does.  (One 32-pixel tile per
+        // image row -- the GEMM form -- so that row tile i starts at row i TH TW; other planes keep the dense order and the test below)
+        if (p.W == TW) {
+            const long long used = row_lim > 0 ? ((long long)row_lim + TH * TW - 1) / (TH * TW) : 0;
+            const long long nb_used = used * tn_groups * p.splits;
+            if (nb_used < (long long)nb) nb = (unsigned)nb_used;
+            if (bid >= nb) return;                                       // (workgroup-uniform, before any barrier)
+        }
+    }
     const unsigned qq = nb / 8, rr = nb % 8, xx = bid % 8, i8 = bid / 8;
     unsigned t = (xx < rr ? xx * (qq + 1) : rr * (qq + 1) + (xx - rr) * qq) + i8;
     const int split = t % p.splits; t /= p.splits;                      // (the splits of a tile side by side: same halo pixels)
-    const int ntn = p.Nc / BN;
-    const int tn_groups = PERSIST ? (ntn + p.ntn_per_wg - 1) / p.ntn_per_wg : ntn;
     const int tng = t % tn_groups; t /= tn_groups;
     const int tn_lo = PERSIST ? tng * p.ntn_per_wg : tng, tn_hi = PERSIST ? min(ntn, tn_lo + p.ntn_per_wg) : tng + 1;
     const int tiles_x = p.W / TW;
@@ -339,11 +354,7 @@ __global__ __launch_bounds__(NT, 2) void bx3_rows_kernel(RowsArgs p) {
     const int x0 = tx * TW, y0 = ty * TH;
     int n0 = tn_lo * BN;
     const int c_beg = split * p.chunks_per_split, c_end = min(p.Kc / CCH, c_beg + p.chunks_per_split);
-    int row_lim = 0x7fffffff;
-    if (NTAP == 1 && UPM == 0 && p.row_limit) {                          // read once per workgroup into an SGPR
-        row_lim = __builtin_amdgcn_readfirstlane(*p.row_limit);
-        if ((b * p.H + y0) * p.W + x0 >= row_lim) return;                // (workgroup-uniform, before any barrier)
-    }
+    if (NTAP == 1 && UPM == 0 && (b * p.H + y0) * p.W + x0 >= row_lim) return;      // (workgroup-uniform, before any barrier)
 
     // halo staging: F4 float4 per pixel and chunk
     constexpr int NF4 = HP * F4, PER = (NF4 + NT - 1) / NT;

@@ -721,10 +721,11 @@ def _head_bwd(xs, dxs, weight, bias, g, relu_inputs=()):
     carr = (ctypes.c_int * len(xs))(*chans)
     flags = sum(1 << (8 + i) for i in relu_inputs) | (2 if direct else 0)
     nmask = sum(chans[i] for i in relu_inputs)
+    cwritten = sum(c for c, d in zip(chans, dxs) if d is not None)       # (a gradient folded into a conv epilogue is not written here)
     _lib.call("t2h_head1x1_bwd", ctypes.cast(xarr, ctypes.c_void_p), ctypes.cast(dxarr, ctypes.c_void_p),
               ctypes.cast(carr, ctypes.c_void_p), len(xs), _lib.ptr(wflat), _lib.ptr(g), b * h * w, flags, _lib.ptr(dw),
               _lib.ptr(db) if db is not None else None, _lib.ptr(ws), ws_bytes, _lib.stream(),
-              nbytes=4 * (2 * ctot + nmask + 1) * b * h * w)
+              nbytes=4 * (ctot + cwritten + nmask + 1) * b * h * w)
     if direct:
         return None, None
     return dw.reshape(weight.shape), db
